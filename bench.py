@@ -3,7 +3,7 @@
 bench.py — headline benchmark of the rasterizer hot path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload S-1080p-1M] [--api vanilla|gsplat]
-                    [--parallelism auto|single|replicated|sharded] [--optimizer fused-adam|none|...]
+                    [--parallelism auto|single|replicated|sharded] [--optimizer fused-adam|none|...] [--dump-outputs DIR]
 
 A "step" is one TRAINING step over one camera of synthetic input: renderer forward (preprocess + SH + binning +
 compositing), the reference's photometric loss, the full backward down to the activated Gaussian properties (means,
@@ -114,6 +114,10 @@ def parse():
     p.add_argument("--init-dist", action="store_true",
                    help="testing only: with --gpus 1, create a process group of ONE rank and issue every collective of the chosen "
                         "--parallelism anyway (the RCCL code paths on a one-GPU machine)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed (rank 0: rendered image, loss, radii, the "
+                        "viewspace gradient, the updated parameters and their gradients, the densification statistics) as "
+                        "DIR/<name>.npy, float32 / float64, at most 64 MB in all (per-Gaussian arrays: a fixed seeded sample of rows)")
     return p.parse_args()
 
 
@@ -320,6 +324,8 @@ def make_step(api, dev, wl, cams, tensors, loss_kind="l1", rank=0, world=1, stre
                 marks.append(_mark())
             state["vs_grad"], state["radii"], state["loss"] = screen.grad, radii, loss
             state["grad_scale"] = None
+            if state.get("keep_render"):          # --dump-outputs only
+                state["render"] = render.detach()
             return state
     else:
         vms = [cam["world_to_camera"].T.contiguous().to(dev) for cam in cams]
@@ -352,6 +358,8 @@ def make_step(api, dev, wl, cams, tensors, loss_kind="l1", rank=0, world=1, stre
             # configs/gsplat-absgrad.yaml:6-8: the density controller reads `viewspace_points.absgrad`
             state["vs_grad"], state["radii"], state["loss"] = (xys.absgrad if absgrad else xys.grad), radii, loss
             state["grad_scale"] = grad_scale
+            if state.get("keep_render"):          # --dump-outputs only
+                state["render"] = img.detach()
             return state
     step.state = state
     return step
@@ -367,6 +375,62 @@ def densification_stats(state, accum, denom, max_radii):
     if req is not None and req.applied:       # HipDensityStatsMixin.update_states: this frame's backward has applied them
         return
     update_densification_stats(state["vs_grad"], None, state["radii"], accum, denom, max_radii, scale=state["grad_scale"])
+
+
+DUMP_BYTES_MAX = 64 << 20      # --dump-outputs: all files together
+DUMP_ROWS = 32768              # per-Gaussian arrays: at most this many rows (a fixed seeded sample, in row order)
+DUMP_IMAGE_VALUES = 8 << 20    # a larger image: this many of its values (a fixed seeded sample, in index order)
+
+
+def dump_outputs(out_dir, state, named_leaves, stats, after_step):
+    """--dump-outputs: what the last timed step computed, as the caller of the step receives it, one float32 / float64 .npy file per
+    array.  The inputs are seeded, so two builds run with the same arguments can be compared file by file; the samples (rows of the
+    per-Gaussian arrays, values of an image too large to keep whole) are drawn from fixed seeds and are the same in every run with the
+    same workload.  `gaussian_rows.npy` names the rows kept; `after_step` (the result line) counts the steps taken, warm-up included."""
+    import numpy as np
+    arrays = {}
+    n = named_leaves[0][1].shape[0]
+    rows = None
+    if n > DUMP_ROWS:
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(1234))[:DUMP_ROWS].sort().values
+        arrays["gaussian_rows"] = rows.double()
+
+    def host(t, per_row=False):
+        t = t.detach()
+        if per_row and rows is not None:
+            t = t[rows.to(t.device)]
+        return t.cpu().double() if t.dtype == torch.float64 else t.cpu().float()
+
+    out = state.get("out")                   # the sharded step keeps the renderer's output dictionary
+    render = out["render"] if out is not None else state["render"]
+    if render.numel() > DUMP_IMAGE_VALUES:
+        keep = torch.randperm(render.numel(), generator=torch.Generator().manual_seed(4321))[:DUMP_IMAGE_VALUES].sort().values
+        arrays["render_sample"] = host(render.reshape(-1)[keep.to(render.device)])
+    else:
+        arrays["render"] = host(render)
+    arrays["loss"] = state["loss"].detach().cpu().double().reshape(())
+    if out is not None:                      # one entry per camera of the step, over this rank's rows
+        arrays["radii"] = torch.stack([host(r[0], True) for r in out["projection_results_list"]], dim=1)
+        grads = [r[1].grad for r in out["projection_results_list"]]
+        if all(g is not None for g in grads):
+            arrays["viewspace_grad"] = torch.stack([host(g, True) for g in grads], dim=1)
+    else:
+        arrays["radii"] = host(state["radii"], True)
+        if state.get("vs_grad") is not None:
+            arrays["viewspace_grad"] = host(state["vs_grad"], True)
+    for name, t in named_leaves:
+        arrays["param_" + name] = host(t, True)
+        if t.grad is not None:
+            arrays["grad_" + name] = host(t.grad, True)
+    for name, t in stats:
+        arrays["stats_" + name] = host(t, True)
+    total = sum(a.numel() * a.element_size() for a in arrays.values())
+    assert total <= DUMP_BYTES_MAX, f"--dump-outputs: {total} bytes (cap {DUMP_BYTES_MAX})"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
+    return {"dir": out_dir, "after_step": after_step, "bytes": total, "rows_of": n, "rows_kept": n if rows is None else int(rows.numel()),
+            "files": {name: list(a.shape) for name, a in arrays.items()}}
 
 
 def cpu_baseline(workload_name, api):
@@ -890,7 +954,16 @@ def main():
             t.grad = None
     ops.LAST_RASTER = None
     the_step = make_full_step(optimizer, args.optimizer)
+    if args.dump_outputs:
+        step.state["keep_render"] = True
     elapsed, prof_graded, _ = timed_region(the_step, args.steps, args.warmup)
+    dumped = None
+    if args.dump_outputs:
+        step.state.pop("keep_render")
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, step.state, list(zip(GROUP_NAMES, tensors)),
+                                  [("grad_accum", accum), ("denom", denom), ("max_radii", max_radii)], counter["n"])
+        step.state.pop("render", None)
     device_mallocs = step.state.get("device_mallocs")
     speculation = dict(ops.SPECULATION)
     # the instrumented pass: the same steps again, with the per-step events
@@ -1108,6 +1181,8 @@ def main():
                                                      if per_cam and "list_entries" in per_cam[0] else None),
                         "per_camera": per_cam if len(per_cam) <= 64 else None},
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if world == 1 and mode == "single" and args.loop == "reference-shaped" and api == "vanilla" and SH_DEGREE == 3:
             try:
                 line["reference_shaped_loop"] = reference_shaped_loop(dev, wl, cam_dicts, args.loop_steps, prewarm=True, view_stream=view_stream)

@@ -9,6 +9,12 @@ def dev():
     return torch.device("cuda:0")
 
 
+# Multi-process GPU tests run at most this many ranks on cuda:0.  Every rank holds the device, and so does the pytest process that
+# started them; the hosts the suite runs on admit six processes with a GPU open, and eight ranks were stopped there.  The eight-way
+# peer transport is exercised at the kernel level in one process (test_peer_exchange.py::test_eight_way_put_signal_wait_in_one_process).
+MAX_RANKS_SHARING_A_GPU = 4
+
+
 def t32(a, device=None):
     return torch.as_tensor(np.asarray(a), dtype=torch.float32).contiguous().to(device or dev())
 

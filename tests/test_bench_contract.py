@@ -26,9 +26,22 @@ def _run(cmd):
 
 
 @pytest.mark.gpu
-def test_single_gpu_line():
-    line = _run([sys.executable, "bench.py", "--workload", "S-800-100k", "--steps", "5", "--warmup", "2"])
+def test_single_gpu_line(tmp_path):
+    line = _run([sys.executable, "bench.py", "--workload", "S-800-100k", "--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path)])
     assert line["n_gpus"] == 1 and line["steps"] == 5 and line["warmup"] == 2 and line["unit"] == "images/s"
+    # --dump-outputs: the last timed step's outputs, float32 / float64, within 64 MB, per-Gaussian arrays on the same sampled rows
+    import numpy as np
+    dumped = line["dumped_outputs"]
+    assert dumped["after_step"] == 2 + 5                      # the last timed step's outputs, not a warm-up step's
+    files = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(files) == set(dumped["files"]) and sum(a.nbytes for a in files.values()) == dumped["bytes"] <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) and list(a.shape) == dumped["files"][k] for k, a in files.items())
+    assert files["render"].shape == (3, 800, 800) and np.isfinite(files["render"]).all() and files["loss"].shape == ()
+    rows = dumped["rows_kept"]
+    assert dumped["rows_of"] == 100_000 and files["gaussian_rows"].shape == (rows,) and files["radii"].shape == (rows,)
+    for k in ("means", "scales", "rotations", "opacities", "shs_dc", "shs_rest"):
+        assert files["param_" + k].shape[0] == rows and np.isfinite(files["param_" + k]).all(), k
+    assert (files["stats_denom"] > 0).any() and (files["radii"] > 0).any()
     assert line["config"]["workload"] == "S-800-100k" and line["config"]["parallelism_mode"] == "single"
     assert abs(line["value"] - 1e3 / line["ms_per_step"]) <= 1e-3 * line["value"]
     assert line["images_per_s_with_optimizer"] == line["value"] and line["images_per_s_renderer_only"] > 0.0      # (5-step regions: no ordering asserted)
@@ -102,27 +115,37 @@ def test_two_rank_launch_line(mode):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["sharded", "replicated"])
-def test_eight_rank_launch_line(mode):
-    """The driver's launch line at the world size BASELINE configs[3] / [4] name (VERDICT r5 #1b): eight processes on the one GPU of
-    the test box (`--share-device`, collectives staged through gloo), both parallelism modes.  One JSON line, last on stdout, `n_gpus`
-    8, whole-job images/s; the sharded mode says which transport passed the validation frame (eight processes mapping each other's
-    IPC buffers on one device can run the peer route — between eight devices the same code runs over xGMI)."""
+def test_four_rank_launch_line(tmp_path, mode):
+    """The driver's launch line with more than two ranks (VERDICT r5 #1b): four processes on the one GPU of the test box, as many as
+    share a device (tests/hip_helpers.MAX_RANKS_SHARING_A_GPU; `--share-device`, collectives staged through gloo), both parallelism
+    modes.  One JSON line, last on stdout, `n_gpus` 4, whole-job images/s; the sharded mode says which transport passed the
+    validation frame (four processes mapping each other's IPC buffers on one device can run the peer route — between devices the
+    same code runs over xGMI)."""
     from conftest import free_port
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(free_port()), "bench.py", "--gpus", "8", "--steps", "3", "--warmup", "1", "--workload", "S-800-100k",
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
+           "--master-port", str(free_port()), "bench.py", "--gpus", "4", "--steps", "3", "--warmup", "1", "--workload", "S-800-100k",
            "--share-device", "--dist-backend", "gloo", "--parallelism", mode]
+    if mode == "sharded":       # rank 0's outputs: its shard's rows, radii and viewspace gradients per camera of the step
+        cmd += ["--dump-outputs", str(tmp_path)]
     line = _run(cmd)
-    assert line["n_gpus"] == 8 and line["scaling"] == "weak" and line["steps"] == 3
+    if mode == "sharded":
+        import numpy as np
+        dumped = line["dumped_outputs"]
+        files = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+        assert set(files) == set(dumped["files"]) and dumped["after_step"] == 1 + 3 and dumped["rows_of"] == dumped["rows_kept"] == 25_000
+        assert files["render"].shape == (3, 800, 800) and files["radii"].shape == (25_000, 4) and files["viewspace_grad"].shape == (25_000, 4, 2)
+        assert files["param_means"].shape == (25_000, 3) and (files["radii"] > 0).any() and np.isfinite(files["render"]).all()
+    assert line["n_gpus"] == 4 and line["scaling"] == "weak" and line["steps"] == 3
     assert line["config"]["parallelism_mode"] == mode
-    assert abs(line["value"] - 8e3 / line["ms_per_step"]) <= 1e-3 * line["value"]               # whole-job images/s
+    assert abs(line["value"] - 4e3 / line["ms_per_step"]) <= 1e-3 * line["value"]               # whole-job images/s
     par = line["config"]["parallelism"]
     if mode == "sharded":
-        assert "sharded over 8 rank(s), 8 camera(s)/step" in par, par
-        # the transport named is the one the timed steps used: peer only after the validation frame on all eight ranks
+        assert "sharded over 4 rank(s), 4 camera(s)/step" in par, par
+        # the transport named is the one the timed steps used: peer only after the validation frame on all four ranks
         assert ("over the peer transport (validated" in par) or ("over the collective transport" in par), par
-        assert "over the peer transport (validated" in par, par      # on one device the eight-way IPC mapping works: the peer route must be taken
+        assert "over the peer transport (validated" in par, par      # on one device the four-way IPC mapping works: the peer route must be taken
     else:
-        assert "replicated Gaussians, 8 camera(s)/step" in par, par
+        assert "replicated Gaussians, 4 camera(s)/step" in par, par
     assert "cpu_baseline" not in line or line["cpu_baseline"] is None                           # rank 0, N = 1 only
     roof = line["roofline"]
     assert roof["intersections"] >= roof["list_entries"] >= roof["entries_walked"] > 0

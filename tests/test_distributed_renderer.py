@@ -411,12 +411,13 @@ def test_world8_sharded_renderer_cpu_oracle_ops(tmp_path, exchange):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("exchange", ["auto", "padded-peer", "counted-peer"])
-def test_world8_sharded_renderer_shared_gpu(tmp_path, exchange):
-    """Eight processes on cuda:0: the 8 x 8 flag matrix of csrc/peer.hip, eight IPC-mapped receive buffers per
-    process, the 8-row mailboxes and count matrix, the 8-camera batched projection / SH launch — at the size they exist for.  Same
+def test_world4_sharded_renderer_shared_gpu(tmp_path, exchange):
+    """Four processes on cuda:0, as many as share one device (tests/hip_helpers.MAX_RANKS_SHARING_A_GPU): the 4 x 4 flag matrix of
+    csrc/peer.hip, four IPC-mapped receive buffers per process, the 4-row mailboxes and count matrix, the 4-camera batched projection
+    / SH launch (the eight-rank run of the same code is test_world8_sharded_renderer_cpu_oracle_ops, on the oracle's ops).  Same
     bar as the two-process test: the peer transports' image bit-equal to the collective route's, gradients home to their owners
     (against the fp64 oracle and the one-process HIP renderer), one forced redistribution with Adam rows."""
-    _run(tmp_path, True, world=8, exchange=exchange)
+    _run(tmp_path, True, world=4, exchange=exchange)
 
 
 @pytest.mark.gpu

@@ -17,7 +17,8 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 def _load(name):
     path = os.path.join(GOLD, name)
     if not os.path.exists(path):
-        pytest.skip(f"{name} not generated yet (needs the upstream CUDA package: see tests/golden/make_upstream_golden.py)")
+        pytest.skip(f"{name} not generated yet: only an NVIDIA GPU with the upstream CUDA package can write it "
+                    "(tests/golden/make_upstream_golden.py)")
     return np.load(path)
 
 
