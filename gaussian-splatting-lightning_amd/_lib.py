@@ -16,7 +16,7 @@ import torch
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSPL_HIP_LIB", os.path.join(_PKG_DIR, "libgspl_hip.so"))   # override: A/B builds of the same ABI
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 GSPL_RECORD_FLOATS = 12
 GSPL_CAMERA_PINHOLE, GSPL_CAMERA_ORTHO, GSPL_CAMERA_FISHEYE = 0, 1, 2
@@ -32,6 +32,8 @@ GSPL_INRIA_NO_SEGMENTS = 2     # ... never segment the backward (the plain one-w
 GSPL_INRIA_FORCE_SEGMENTS = 4  # ... always (default: adaptively, while walks longer than a segment are being met)
 GSPL_INRIA_WILL_BACKWARD = 8   # ... IN: a backward follows: the forward clears the backward's packed rows (GSPL_BUF_PACKED)
 GSPL_INRIA_PACKED_READY = 16   # ... OUT: it did
+GSPL_INRIA_ANTIALIAS = 32      # ... IN (ABI 36): opacity * sqrt(max(2.5e-5, det0 / det1)), the Mip-Splatting 2D filter
+GSPL_INRIA_INVDEPTH = 128      # ... IN (ABI 36): a 4th composited channel, 1 / z (out [4,H,W], bg of 4 values, packed rows of 10)
 GSPL_BIN_SPAN_BYTES = 64
 GSPL_ADAM_MAX_TENSORS = 16
 

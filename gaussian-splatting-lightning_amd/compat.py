@@ -1,7 +1,8 @@
 """Import shims for the reference's un-vendored native packages that this package replaces.
 
-Besides the two small helpers below (`simple_knn`, `fused_ssim`), `install()` registers stand-ins for the two rasterizer
-packages themselves — `diff_gaussian_rasterization` and the yzslab `gsplat` fork — under the module paths and function names the
+Besides the two small helpers below (`simple_knn`, `fused_ssim`), `install()` registers stand-ins for the rasterizer
+packages themselves — `diff_gaussian_rasterization`, Taming 3DGS's `diff_accel_gaussian_rasterization` and the yzslab `gsplat`
+fork — under the module paths and function names the
 reference imports (internal/renderers/vanilla_renderer.py:4, gsplat_renderer.py:2-4, gsplat_v1_renderer.py:8-20,
 pypreprocess_gsplat_renderer.py:1-2, gsplat_hit_pixel_count_renderer.py:5, internal/optimizers.py:34 ...), each bound to the HIP
 op of `gspl_amd.ops` with the same signature.  With them the reference's OWN renderer classes (`VanillaRenderer`,
@@ -91,6 +92,14 @@ def _install_rasterizer_packages(installed: list):
         _module("diff_gaussian_rasterization", "gspl_amd stand-in for diff_gaussian_rasterization (HIP; gspl_amd.ops.GaussianRasterizer)",
                 GaussianRasterizationSettings=ops.GaussianRasterizationSettings, GaussianRasterizer=ops.GaussianRasterizer)
         installed.append("diff_gaussian_rasterization")
+    if _missing("diff_accel_gaussian_rasterization"):
+        from . import ops, optimizers
+        _module("diff_accel_gaussian_rasterization",
+                "gspl_amd stand-in for diff_accel_gaussian_rasterization (Taming 3DGS; HIP: gspl_amd.ops.AccelGaussianRasterizer, "
+                "gspl_amd.optimizers.SparseGaussianAdam)",
+                GaussianRasterizationSettings=ops.AccelRasterizationSettings, GaussianRasterizer=ops.AccelGaussianRasterizer,
+                SparseGaussianAdam=optimizers.SparseGaussianAdam)
+        installed.append("diff_accel_gaussian_rasterization")
     if _missing("gsplat"):
         doc = "gspl_amd stand-in for the gsplat fork (HIP ops of gspl_amd.ops under the fork's module paths)"
         pkg = _module("gsplat", doc, spherical_harmonics=_late("spherical_harmonics"))

@@ -92,10 +92,12 @@ __global__ __launch_bounds__(64) void composite_fwd_kernel(
     if (!__all(done)) {
         int g_next = (start + l < end) ? flatten_ids[start + l] : 0;
         for (int base = start; base < end; base += FCHUNK) {
-            if constexpr (D == 3) {
+            if constexpr (D == 3 || (D == 4 && MODE == GSPL_MODE_INRIA)) {
                 // segmented backward: every pixel's state in front of list position `base`, each SEG entries (gspl_composite.h)
                 if (seg.ckpt && base > start && (((base - start) & (SEG - 1)) == 0)) {
-                    seg.ckpt[(size_t)((unsigned)base >> SEG_LOG2) * 256u + (unsigned)(w * 64 + l)] = make_float4(T, acc[0], acc[1], acc[2]);
+                    const size_t ci = (size_t)((unsigned)base >> SEG_LOG2) * 256u + (unsigned)(w * 64 + l);
+                    seg.ckpt[ci] = make_float4(T, acc[0], acc[1], acc[2]);
+                    if constexpr (D == 4) { seg.ckpt_x[ci] = acc[3]; acc[3] = 0.f; }
                     acc[0] = acc[1] = acc[2] = 0.f;      // the colour restarts with every segment (see below)
                     ++n_ckpt;
                 }
@@ -171,15 +173,17 @@ __global__ __launch_bounds__(64) void composite_fwd_kernel(
         }
     }
 
-    if constexpr (D == 3) {
+    if constexpr (D == 3 || (D == 4 && MODE == GSPL_MODE_INRIA)) {
         if (seg.ckpt) {
             if (blockIdx.x == 0 && l < 2) seg.words[l] = 0u;      // the backward's item counter is zero when the backward starts
             // checkpoint k holds the colour of segment k - 1 and `acc` that of the last one: suffix sums from the back (every lane
             // rewrites its own pixel's entries), and the image = the sum of all segments
             for (int k = n_ckpt; k >= 1; --k) {
-                float4* c = seg.ckpt + (size_t)((unsigned)(start + k * SEG) >> SEG_LOG2) * 256u + (unsigned)(w * 64 + l);
+                const size_t ci = (size_t)((unsigned)(start + k * SEG) >> SEG_LOG2) * 256u + (unsigned)(w * 64 + l);
+                float4* c = seg.ckpt + ci;
                 const float4 v = *c;
                 *c = make_float4(v.x, acc[0], acc[1], acc[2]);
+                if constexpr (D == 4) { const float x = seg.ckpt_x[ci]; seg.ckpt_x[ci] = acc[3]; acc[3] += x; }
                 acc[0] += v.y; acc[1] += v.z; acc[2] += v.w;
             }
         }
@@ -206,7 +210,8 @@ static int launch_fwd(int n_tiles, int tile_w, int width, int height, int64_t n_
                       float* out_colors, float* out_alphas, float* final_Ts, int32_t* last_ids, uint8_t* hit_flags, hipStream_t s, ListTiles lt,
                       const SegState* seg_in) {
     SegState seg = {};
-    if (seg_in && D == 3 && lt.log2 == 4) seg = *seg_in;      // checkpoints: 16-pixel list tiles, three channels
+    // checkpoints: 16-pixel list tiles, three channels (or four in the Inria mode, with the 4th channel's array)
+    if (seg_in && lt.log2 == 4 && (D == 3 || (D == 4 && MODE == GSPL_MODE_INRIA && (!seg_in->ckpt || seg_in->ckpt_x)))) seg = *seg_in;
     else if (seg_in) { seg.zero_p = seg_in->zero_p; seg.zero_n16 = seg_in->zero_n16; }
     if (hit_flags)
         hipLaunchKernelGGL((composite_fwd_kernel<D, MODE, CHW, true>), dim3(4 * n_tiles), dim3(64), 0, s,

@@ -176,10 +176,10 @@ __global__ __launch_bounds__(B2_NT, GSPL_BWD2_WAVES) void composite_bwd2_kernel(
                 for (int e = 0; e < 2; ++e) {
                     if (lasts[e] > seg_hi) {
                         const float4 ck = seg.ckpt[slot + (unsigned)((2 * w + e) * 64 + l)];
-                        const float ckc[3] = {ck.y, ck.z, ck.w};
+                        const float ckc[4] = {ck.y, ck.z, ck.w, D == 4 ? seg.ckpt_x[slot + (unsigned)((2 * w + e) * 64 + l)] : 0.f};
                         float behind = 0.f;
 #pragma unroll
-                        for (int c = 0; c < D; ++c) behind = fmaf(e == 0 ? vo[c].x : vo[c].y, ckc[c < 3 ? c : 0], behind);
+                        for (int c = 0; c < D; ++c) behind = fmaf(e == 0 ? vo[c].x : vo[c].y, ckc[c < 4 ? c : 0], behind);
                         Tn[e] = ck.x;
                         Rn[e] = Rn[e] - behind;
                     }
@@ -557,10 +557,10 @@ static int launch_bwd(bool absgrad, int n_tiles, int tile_w, int width, int heig
     }
     SegState plain = {};
     if (seg_in) { plain.host_flag = seg_in->host_flag; plain.walk = seg_in->walk; }
-    if constexpr (D == 3 && CHW && PACKED) {
+    if constexpr ((D == 3 || (D == 4 && MODE == GSPL_MODE_INRIA)) && CHW && PACKED) {
         // the segmented form (the fused Inria call with checkpoints from its forward): regular gradients only — the deterministic mode
         // and absgrad keep the one-workgroup-per-tile walk
-        if (seg_in && seg_in->ckpt && !absgrad && packed_stride > 0) {
+        if (seg_in && seg_in->ckpt && (D == 3 || seg_in->ckpt_x) && !absgrad && packed_stride > 0) {
             hipLaunchKernelGGL((composite_bwd2_kernel<D, MODE, CHW, false, PACKED, 1>), dim3(n_tiles), dim3(B2_NT), 0, s, GSPL_BWD_ARGS, *seg_in);
             hipLaunchKernelGGL((composite_bwd2_kernel<D, MODE, CHW, false, PACKED, 2>), dim3(seg_in->slots), dim3(B2_NT), 0, s, GSPL_BWD_ARGS, *seg_in);
             return check_launch("composite_bwd(segmented)");

@@ -24,9 +24,10 @@ static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // per-splat intermediates of one frame, carved out of ONE allocation (tag GSPL_BUF_GEOMETRY)
 struct GeomLayout {
-    size_t radii, means2d, depths, conics, colors, clamped, cov3d, sh_jac, order, cum, big_list, spans, opac, total;
+    size_t radii, means2d, depths, conics, colors, clamped, cov3d, sh_jac, order, cum, big_list, spans, opac, colors4, total;
 };
-static GeomLayout geom_layout(size_t n) {
+// invdepth (GSPL_INRIA_INVDEPTH): one more region, the [N,4] rows compositing reads (colour | 1 / z)
+static GeomLayout geom_layout(size_t n, bool invdepth = false) {
     GeomLayout g;
     size_t off = 0;
     auto take = [&](size_t b) { size_t o = off; off = up256(off + b); return o; };
@@ -34,6 +35,7 @@ static GeomLayout geom_layout(size_t n) {
     g.clamped = take(3 * n); g.cov3d = take(24 * n); g.sh_jac = take(36 * n);
     g.order = take(4 * n); g.cum = take(8 * (n + 1)); g.big_list = take(4 * n); g.spans = take((size_t)GSPL_BIN_SPAN_BYTES * n);
     g.opac = take(4 * n);
+    g.colors4 = invdepth ? take(16 * n) : 0;
     g.radii = 0;       // radii are an OUTPUT tensor of the call, not part of the block
     g.total = off;
     return g;
@@ -264,14 +266,18 @@ extern "C" int gspl_rasterize_inria_fwd(
     const int tile = 16, tile_w = (width + 15) / 16, tile_h = (height + 15) / 16, n_tiles = tile_w * tile_h;
     hipStream_t s = (hipStream_t)stream, ss = (hipStream_t)side_stream;
     const int flags = st->flags;
-    if (flags & ~(GSPL_INRIA_RAW_PARAMS | GSPL_INRIA_NO_SEGMENTS | GSPL_INRIA_FORCE_SEGMENTS | GSPL_INRIA_WILL_BACKWARD)) return fail_arg("rasterize_inria_fwd: unknown state->flags (zero the struct before the call)");
+    if (flags & ~(GSPL_INRIA_RAW_PARAMS | GSPL_INRIA_NO_SEGMENTS | GSPL_INRIA_FORCE_SEGMENTS | GSPL_INRIA_WILL_BACKWARD | GSPL_INRIA_ANTIALIAS |
+                  GSPL_INRIA_INVDEPTH)) return fail_arg("rasterize_inria_fwd: unknown state->flags (zero the struct before the call)");
     const bool raw = (flags & GSPL_INRIA_RAW_PARAMS) != 0;
+    const bool aa = (flags & GSPL_INRIA_ANTIALIAS) != 0, invd = (flags & GSPL_INRIA_INVDEPTH) != 0;
+    const int D = invd ? 4 : 3;                  // composited channels: colour (| inverse depth)
+    const int prow = invd ? 10 : 9;              // the backward's packed row: x y | a b c | opacity | colour channels
     if (raw && (cov3D_precomp || (N > 0 && (!scales || !rotations)))) return fail_arg("rasterize_inria_fwd: raw parameters need scales and rotations");
     memset(st, 0, sizeof(*st));
     st->flags = flags;
     st->N = N; st->width = width; st->height = height;
     const size_t n = (size_t)(N > 0 ? N : 1);
-    const GeomLayout g = geom_layout(n);
+    const GeomLayout g = geom_layout(n, invd);
     const ImageLayout im = image_layout((size_t)width * height, (size_t)n_tiles);
     char* geom = (char*)alloc(alloc_ctx, GSPL_BUF_GEOMETRY, g.total);
     char* img = (char*)alloc(alloc_ctx, GSPL_BUF_IMAGE, im.total);
@@ -279,8 +285,10 @@ extern "C" int gspl_rasterize_inria_fwd(
     st->means2d = (float*)(geom + g.means2d); st->depths = (float*)(geom + g.depths); st->conics = (float*)(geom + g.conics);
     st->colors = (float*)(geom + g.colors); st->clamped = (uint8_t*)(geom + g.clamped); st->cov3d = (float*)(geom + g.cov3d);
     st->sh_jac = (float*)(geom + g.sh_jac);
-    const float* raw_opacities = raw ? opacities : nullptr;
-    if (raw) opacities = (float*)(geom + g.opac);          // from here on: what binning and compositing read
+    float* colors3 = st->colors;                  // where the colour kernel writes; with invd compositing reads the [N,4] rows
+    if (invd) st->colors = (float*)(geom + g.colors4);
+    const float* raw_opacities = (raw || aa) ? opacities : nullptr;      // (with aa: the caller's opacities, raw or activated)
+    if (raw || aa) opacities = (float*)(geom + g.opac);          // from here on: what binning and compositing read
     st->opacities = const_cast<float*>(opacities);
     st->alphas = (float*)(img + im.alphas); st->final_Ts = (float*)(img + im.final_Ts); st->last_ids = (int32_t*)(img + im.last_ids);
     st->offsets = (int32_t*)(img + im.offsets);
@@ -297,7 +305,7 @@ extern "C" int gspl_rasterize_inria_fwd(
     uint4* packed_zero = nullptr;
     uint32_t packed_n16 = 0u;
     if ((flags & GSPL_INRIA_WILL_BACKWARD) && N > 0) {
-        const size_t bytes = ((size_t)N * 9 * sizeof(float) + 15) & ~(size_t)15;
+        const size_t bytes = ((size_t)N * prow * sizeof(float) + 15) & ~(size_t)15;
         packed_zero = (uint4*)alloc(alloc_ctx, GSPL_BUF_PACKED, bytes);
         if (packed_zero && bytes / 16 <= 0xffffffffull) { packed_n16 = (uint32_t)(bytes / 16); st->flags |= GSPL_INRIA_PACKED_READY; }
         else packed_zero = nullptr;
@@ -311,11 +319,13 @@ extern "C" int gspl_rasterize_inria_fwd(
         const uint32_t slots = (uint32_t)(cap >> SEG_LOG2) + 2u;
         const size_t words = 2 + (size_t)slots;
         const size_t head = up256(words * sizeof(uint32_t));
-        char* blk = (char*)alloc(alloc_ctx, GSPL_BUF_CHECKPOINTS, head + (size_t)slots * 256 * sizeof(float4));
+        // (with invd: one more float per checkpoint, the inverse-depth channel, after the float4s)
+        char* blk = (char*)alloc(alloc_ctx, GSPL_BUF_CHECKPOINTS, head + (size_t)slots * 256 * (sizeof(float4) + (invd ? sizeof(float) : 0)));
         if (!blk) return (adaptive || packed_zero) ? &seg : nullptr;
         uint32_t* wds = (uint32_t*)blk;
         seg.words = wds; seg.slots = slots;      // (the item counter is cleared by the forward kernel itself)
         seg.ckpt = (float4*)(blk + head);
+        seg.ckpt_x = invd ? (float*)(seg.ckpt + (size_t)slots * 256) : nullptr;
         st->seg_ckpt = seg.ckpt; st->seg_words = wds; st->seg_slots = slots;
         return &seg;
     };
@@ -353,7 +363,8 @@ extern "C" int gspl_rasterize_inria_fwd(
         if (rc == GSPL_OK && ws2) rc = bin_tile_header(N, capacity, tile_w * tile_h, ws2, zero_tile);
         if (rc != GSPL_OK) return rc;
         rc = inria_geometry_launch(N, means3D, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, width, height, tile, tanfovx, tanfovy, scale_modifier,
-                                   radii, st->means2d, st->depths, st->conics, st->cov3d, raw_opacities, st->opacities, s, zero_depth);
+                                   radii, st->means2d, st->depths, st->conics, st->cov3d, raw_opacities, st->opacities, s, zero_depth,
+                                   flags & (GSPL_INRIA_RAW_PARAMS | GSPL_INRIA_ANTIALIAS));
         if (rc != GSPL_OK) return rc;
         FrameEvents& fe = frame_events();
         if (!fe.ok) return check_hip(hipGetLastError(), "rasterize_inria_fwd: event");
@@ -366,7 +377,8 @@ extern "C" int gspl_rasterize_inria_fwd(
         hipStream_t cs = (ss && ss != s) ? ss : s;
         rc = gspl_inria_preprocess_fwd(N, degree, n_coeffs, means3D, scales, rotations, cov3D_precomp, shs, shs_rest, colors_precomp, viewmatrix, projmatrix,
                                        campos, width, height, tile, tanfovx, tanfovy, scale_modifier, radii, st->means2d, st->depths, st->conics,
-                                       st->colors, st->clamped, st->cov3d, st->sh_jac, GSPL_INRIA_COLOURS, cs);
+                                       colors3, st->clamped, st->cov3d, st->sh_jac, GSPL_INRIA_COLOURS, cs);
+        if (rc == GSPL_OK && invd) rc = inria_invdepth_rows_launch(N, radii, colors3, st->depths, st->colors, cs);      // (on the colour stream)
         if (rc == GSPL_OK && ev_col) (void)hipEventRecord(ev_col, cs);
         if (rc != GSPL_OK) return rc;
         {
@@ -393,7 +405,7 @@ extern "C" int gspl_rasterize_inria_fwd(
                 if (ev_col) (void)hipStreamWaitEvent(s, ev_col, 0);      // colours are ready before compositing reads them
                 {
                     ProfScope prof(0, s);
-                    rc = composite_fwd_impl(N, -1, 3, GSPL_MODE_INRIA, GSPL_LAYOUT_CHW, st->means2d, st->conics, st->colors, opacities, bg, width, height,
+                    rc = composite_fwd_impl(N, -1, D, GSPL_MODE_INRIA, GSPL_LAYOUT_CHW, st->means2d, st->conics, st->colors, opacities, bg, width, height,
                                             tile, tile_w, tile_h, st->offsets, st->flatten_ids, out_color, st->alphas, st->final_Ts, st->last_ids, nullptr, s, sg);
                 }
                 const bool arrived = wait_count();
@@ -432,7 +444,7 @@ extern "C" int gspl_rasterize_inria_fwd(
     }
     st->n_isects = n_isects;
     ProfScope prof(0, s);
-    return composite_fwd_impl(N, n_isects, 3, GSPL_MODE_INRIA, GSPL_LAYOUT_CHW, st->means2d, st->conics, st->colors, opacities, bg, width, height, tile,
+    return composite_fwd_impl(N, n_isects, D, GSPL_MODE_INRIA, GSPL_LAYOUT_CHW, st->means2d, st->conics, st->colors, opacities, bg, width, height, tile,
                               tile_w, tile_h, st->offsets, st->flatten_ids, out_color, st->alphas, st->final_Ts, st->last_ids, nullptr, s,
                               (seg.ckpt || seg.walk || seg.zero_p) ? &seg : nullptr);
 }
@@ -476,6 +488,8 @@ extern "C" int gspl_rasterize_inria_bwd_adam(
     float* packed, uint8_t* hit_flags, float* scratch_means, float* v_means2D_ndc, const gspl_bwd_adam_plan* plan, void* stream) {
     if (!plan) return gspl::fail_arg("rasterize_inria_bwd_adam: NULL plan");
     if (!scales || !rotations || !shs || !opacities) return gspl::fail_arg("rasterize_inria_bwd_adam: needs scales, rotations, SH coefficients and opacities");
+    if (st && (st->flags & (GSPL_INRIA_ANTIALIAS | GSPL_INRIA_INVDEPTH)))
+        return gspl::fail_arg("rasterize_inria_bwd_adam: a frame rendered with GSPL_INRIA_ANTIALIAS or GSPL_INRIA_INVDEPTH takes gspl_rasterize_inria_bwd and a separate optimizer");
     return gspl::rasterize_inria_bwd_impl(degree, n_coeffs, means3D, scales, rotations, shs, shs_rest, opacities, viewmatrix, projmatrix, campos, bg,
                                           tanfovx, tanfovy, scale_modifier, radii, st, v_out_color, packed, hit_flags, scratch_means, v_means2D_ndc, shs,
                                           shs_rest, nullptr, opacities, scales, rotations, nullptr, stream, plan);
@@ -487,7 +501,7 @@ static int gspl::rasterize_inria_bwd_impl(
     const float* viewmatrix, const float* projmatrix, const float* campos, const float* bg,
     float tanfovx, float tanfovy, float scale_modifier,
     const int32_t* radii, const gspl_inria_state* st, const float* v_out_color,
-    float* packed /* [N, 9] scratch */, uint8_t* hit_flags,
+    float* packed /* [N, 9] scratch ([N, 10] with GSPL_INRIA_INVDEPTH) */, uint8_t* hit_flags,
     float* v_means3D, float* v_means2D_ndc, float* v_shs, float* v_shs_rest, float* v_colors_precomp, float* v_opacities,
     float* v_scales, float* v_rotations, float* v_cov3D, void* stream, const gspl_bwd_adam_plan* plan) {
     using namespace gspl;
@@ -498,8 +512,11 @@ static int gspl::rasterize_inria_bwd_impl(
     const int tile = 16, tile_w = (width + 15) / 16, tile_h = (height + 15) / 16;
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipSuccess;
+    const bool aa = (st->flags & GSPL_INRIA_ANTIALIAS) != 0, invd = (st->flags & GSPL_INRIA_INVDEPTH) != 0;
+    const int D = invd ? 4 : 3, prow = invd ? 10 : 9;
+    const float* caller_opacities = opacities;      // (aa: the backward of the compensation reads them, raw or activated)
     if (!(st->flags & GSPL_INRIA_PACKED_READY)) {      // (else `packed` is the forward's GSPL_BUF_PACKED block, cleared by its compositing kernel)
-        e = hipMemsetAsync(packed, 0, (size_t)N * 9 * sizeof(float), s);      // x y | a b c | opacity | r g b
+        e = hipMemsetAsync(packed, 0, (size_t)N * prow * sizeof(float), s);      // x y | a b c | opacity | r g b (| 1/z)
         if (e != hipSuccess) return check_hip(e, "rasterize_inria_bwd: clear");
     }
     if (hit_flags) {
@@ -512,21 +529,27 @@ static int gspl::rasterize_inria_bwd_impl(
         if (!st->opacities || !v_scales || !v_rotations) return fail_arg("rasterize_inria_bwd: raw parameters need the forward's state, v_scales and v_rotations");
         opacities = st->opacities;         // the activated values the forward composited with
     }
+    if (aa) {
+        if (!st->opacities) return fail_arg("rasterize_inria_bwd: anti-aliasing needs the forward's state");
+        opacities = st->opacities;         // opacity * comp, what the forward composited with
+    }
     if (st->n_isects > 0) {
         SegState seg = {};
         if (st->seg_ckpt && st->seg_words) {      // the forward left checkpoints: long walks are cut into segments (gspl_composite.h)
             seg.ckpt = (float4*)st->seg_ckpt;
             seg.words = st->seg_words; seg.slots = st->seg_slots;
+            if (invd) seg.ckpt_x = (float*)(seg.ckpt + (size_t)seg.slots * 256);      // the inverse-depth channel's checkpoints
         }
         if (!(st->flags & GSPL_INRIA_NO_SEGMENTS) && gspl_get_deterministic() == 0) seg.walk = seg_walk_words();      // plain or segmented: the walk lengths are left for the next forward
         ProfScope prof(1, s);
-        rc = composite_bwd_packed_impl(N, st->n_isects, 3, GSPL_MODE_INRIA, GSPL_LAYOUT_CHW, st->means2d, st->conics, st->colors, opacities, bg, width,
+        rc = composite_bwd_packed_impl(N, st->n_isects, D, GSPL_MODE_INRIA, GSPL_LAYOUT_CHW, st->means2d, st->conics, st->colors, opacities, bg, width,
                                        height, tile, tile_w, tile_h, st->offsets, st->flatten_ids, st->final_Ts, st->last_ids, v_out_color, nullptr,
-                                       packed, 9, 0, hit_flags, s, &seg);
+                                       packed, prow, 0, hit_flags, s, &seg);
         if (rc != GSPL_OK) return rc;
     }
     return inria_preprocess_bwd_impl(N, degree, n_coeffs, means3D, scales, rotations, st->cov3d, shs, shs_rest, viewmatrix, projmatrix, campos, width, height,
-                                     tanfovx, tanfovy, scale_modifier, radii, st->clamped, packed, packed + 2, packed + 6, 9, v_means3D, v_scales,
+                                     tanfovx, tanfovy, scale_modifier, radii, st->clamped, packed, packed + 2, packed + 6, prow, v_means3D, v_scales,
                                      v_rotations, v_cov3D, v_shs, v_shs_rest, v_colors_precomp, v_means2D_ndc, packed + 5, v_opacities, st->sh_jac,
-                                     raw ? st->opacities : nullptr, s, plan, BwdStats{st->stats_accum, st->stats_denom, st->stats_max_radii});
+                                     aa ? caller_opacities : (raw ? st->opacities : nullptr), s, plan, BwdStats{st->stats_accum, st->stats_denom, st->stats_max_radii},
+                                     st->flags & (GSPL_INRIA_RAW_PARAMS | GSPL_INRIA_ANTIALIAS | GSPL_INRIA_INVDEPTH));
 }

@@ -150,7 +150,8 @@ __device__ __forceinline__ unsigned band_half_mask(float mx, float my, float a, 
 //             view of the metric workload's heterogeneous set (-131 us), which a per-stream switch could not take without dragging the
 //             fifteen views that lose 14-61 us along.  (Round 5's trigger was the length alone: close-up views of the uniform cloud walk
 //             800-1000 entries in EVERY tile — no tail, nothing to spread — and paid 38 us for checkpoints and a second launch.)
-// D == 3 only (a checkpoint is one float4); off (ckpt == nullptr) everywhere else.
+// D == 3 (a checkpoint is one float4), and D == 4 in the Inria mode (the fused call's inverse-depth channel, GSPL_INRIA_INVDEPTH: the
+// float4 holds T and the three colours, `ckpt_x` — same slot index, one float — the 4th channel); off (ckpt == nullptr) everywhere else.
 #ifndef GSPL_SEG_LOG2
 #define GSPL_SEG_LOG2 8      // 256 entries per segment (measured on scene_surfaces, per step: 64 -> 1.63 ms, 128 -> 1.45, 256 -> 1.47, 512 -> 1.56, 1024 -> 1.72;
                              // 128 costs the forward 4 % more for its checkpoints and twice the checkpoint memory: profiles/r07v_segment_sizes.txt)
@@ -170,6 +171,7 @@ struct SegState {
     uint4* zero_p;        // forward only: a block this launch clears on behalf of the backward (its packed rows: GSPL_BUF_PACKED), 16-byte units
     uint32_t zero_n16;
     uint32_t slots;
+    float* ckpt_x;        // D == 4: the 4th channel of every checkpoint (indexed as ckpt); nullptr with D == 3
     __host__ __device__ uint32_t* count() const { return words; }
     __host__ __device__ uint32_t* work() const { return words + 2; }
 };

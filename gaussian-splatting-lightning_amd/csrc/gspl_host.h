@@ -73,7 +73,10 @@ int inria_geometry_launch(int N, const float* means, const float* scales, const 
                           float tanfovx, float tanfovy, float scale_modifier,
                           int32_t* radii, float* means2d, float* depths, float* conics, float* cov3d,
                           const float* raw_opacities /* nullable: activated parameters */, float* opacities_out, hipStream_t s,
-                          ZeroJob zero = ZeroJob() /* cleared by the same kernel, for the binning that follows */);
+                          ZeroJob zero = ZeroJob() /* cleared by the same kernel, for the binning that follows */,
+                          int ext = 0 /* GSPL_INRIA_ANTIALIAS (+ GSPL_INRIA_RAW_PARAMS): raw_opacities = the caller's opacities, raw or not */);
+// [N,4] rows colour | 1 / z for the inverse-depth channel of the fused call (GSPL_INRIA_INVDEPTH); colors4 16-byte aligned
+int inria_invdepth_rows_launch(int N, const int32_t* radii, const float* colors3, const float* depths, float* colors4, hipStream_t s);
 int inria_preprocess_bwd_impl(int N, int degree, int n_coeffs, const float* means, const float* scales, const float* quats,
                               const float* cov3d, const float* shs, const float* shs_rest,
                               const float* viewmatrix, const float* projmatrix, const float* campos,
@@ -86,5 +89,6 @@ int inria_preprocess_bwd_impl(int N, int degree, int n_coeffs, const float* mean
                               const float* opac_act /* nullable: activated parameters */, void* stream,
                               const gspl_bwd_adam_plan* adam = nullptr /* not NULL: v_shs / v_shs_rest / v_scales / v_quats / v_opacities are
                               the PARAMETERS (as means, scales, quats are), updated in place; v_means is scratch [N,3] */,
-                              BwdStats stats = BwdStats());
+                              BwdStats stats = BwdStats(),
+                              int ext = 0 /* GSPL_INRIA_ANTIALIAS / GSPL_INRIA_INVDEPTH (+ GSPL_INRIA_RAW_PARAMS): see inria.hip */);
 }  // namespace gspl

@@ -74,6 +74,7 @@ struct InriaGeom {
     float Wstd[9];      // standard-orientation rotation (row i, col j) = V[j*4+i]
     EwaCtx ctx;
     float a, b, c;      // blurred cov2D
+    float a0, c0;       // ... its diagonal before the +0.3 (the anti-aliasing compensation; b is not blurred)
     float det;
     float fx, fy;
 };
@@ -95,6 +96,7 @@ __device__ __forceinline__ bool inria_geom(const InriaCam& cam, const float p[3]
     G.fy = (float)height / (2.f * tanfovy);
     float a0, b0, c0;
     ewa_fwd(G.pv, G.S6, G.Wstd, G.fx, G.fy, 1.3f * tanfovx, 1.3f * tanfovy, a0, b0, c0, G.ctx);
+    G.a0 = a0; G.c0 = c0;
     G.a = a0 + 0.3f; G.b = b0; G.c = c0 + 0.3f;
     G.det = G.a * G.c - G.b * G.b;
     return G.det != 0.f;
@@ -108,7 +110,20 @@ __device__ __forceinline__ bool inria_geom(const InriaCam& cam, const float p[3]
 __device__ __forceinline__ float act_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ float act_quat_norm(const float q[4]) { return fmaxf(sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]), 1e-12f); }
 
-template <bool RAW>
+// Anti-aliasing (GSPL_INRIA_ANTIALIAS): the Mip-Splatting 2D filter on the Inria API, restated from the published rule (graphdeco
+// `dr_aa` rasterizer, Taming 3DGS): det0 = a0 c0 - b^2 of the 2D covariance BEFORE the +0.3 dilation, det1 = a c - b^2 after it,
+//   comp = sqrt(max(2.5e-5, det0 / det1)),
+// and the opacity compositing and the binning's tile culling read is opacity * comp (radii and conics already use the dilated
+// covariance).  Returns the ratio det0 / det1 (the backward's floor test) through `ratio`.
+__device__ __forceinline__ float aa_compensation(const InriaGeom& G, float& ratio) {
+    const float det0 = G.a0 * G.c0 - G.b * G.b;
+    ratio = det0 / G.det;
+    return sqrtf(fmaxf(2.5e-5f, ratio));
+}
+
+// AA: `raw_opacities` are the opacities as the caller passed them (raw with RAW, activated without) and `opacities_out` receives the
+// effective ones, activation(opacity) * comp (see aa_compensation; rows the geometry culls keep comp = 1).
+template <bool RAW, bool AA = false>
 __global__ __launch_bounds__(256) void inria_preprocess_fwd_kernel(
     int N,
     const float* __restrict__ means, const float* __restrict__ scales, const float* __restrict__ quats,
@@ -137,6 +152,7 @@ __global__ __launch_bounds__(256) void inria_preprocess_fwd_kernel(
     float S6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int o_radius = 0;
     float o_xy[2] = {0.f, 0.f}, o_depth = 0.f, o_conic[3] = {0.f, 0.f, 0.f};
+    float o_comp = 1.f;
     if (t < rows) {
         InriaCam cam;
         load_inria_cam(viewmatrix, projmatrix, cam);
@@ -163,6 +179,7 @@ __global__ __launch_bounds__(256) void inria_preprocess_fwd_kernel(
         }
         InriaGeom G;
         if (inria_geom(cam, p, S6, width, height, tanfovx, tanfovy, G)) {
+            if constexpr (AA) { float ratio; o_comp = aa_compensation(G, ratio); }
             const float inv_det = 1.f / G.det;
             const float mid = 0.5f * (G.a + G.c);
             const float lambda = mid + sqrtf(fmaxf(0.1f, mid * mid - G.det));
@@ -185,7 +202,8 @@ __global__ __launch_bounds__(256) void inria_preprocess_fwd_kernel(
         }
         radii[g] = o_radius;            // 4-byte columns: already one full line per 32 lanes
         depths[g] = o_depth;
-        if constexpr (RAW) opacities_out[g] = act_sigmoid(raw_opacities[g]);
+        if constexpr (AA) opacities_out[g] = (RAW ? act_sigmoid(raw_opacities[g]) : raw_opacities[g]) * o_comp;
+        else if constexpr (RAW) opacities_out[g] = act_sigmoid(raw_opacities[g]);
     }
     __syncthreads();                    // every lane has read its input rows: the memory now takes the output rows
     float* s_cov = s_buf;
@@ -213,6 +231,12 @@ __global__ __launch_bounds__(256) void inria_preprocess_fwd_kernel(
 // the kernel applies the Adam update to the rows of means, scales, rotations and opacities it has just produced the gradient of
 // (`adam`: parameter, moments, hyper-parameters; every row, the invisible ones with a zero gradient, as torch.optim.Adam does).
 // The parameters are read and written through `adam.*.p` (no __restrict__ promise on memory this kernel writes).
+// AA (GSPL_INRIA_ANTIALIAS; never with ADAM): the composited opacity was o * comp (aa_compensation), `opac_act` = the opacities as the
+// caller passed them (raw with RAW).  With g the compositing's gradient of the effective opacity: v_opacity = g comp (times o (1 - o)
+// with RAW), and v_comp = g o flows through comp = sqrt(det0 / det1) into the UNDILATED 2D covariance next to the conic's gradient
+// (zero at the 2.5e-5 floor), from there into cov3D and the scales / rotations (or cov3D_precomp) as the conic's does.
+// INVD (GSPL_INRIA_INVDEPTH): the packed row carries a 4th colour column, the gradient of the composited 1 / z: v_z = -v_invd / z^2
+// joins the view-space mean's gradient (z = the view-space depth the forward composited the inverse of).
 struct PreAdam { AdamTarget means, scales, quats, opac; };
 // Adam over `total` consecutive floats of one parameter starting at float `base` (a block's rows), gradients in LDS: 16-byte chunks
 // per lane, coalesced; a slice that is not 16-byte aligned, and the last partial chunk, go element by element.
@@ -243,7 +267,7 @@ __device__ __forceinline__ void pre_adam_pass(const AdamTarget& T, int64_t base,
         gp[e] = p; gm[e] = m; gv[e] = v;
     }
 }
-template <bool ACCUM, bool RAW, bool ADAM = false>
+template <bool ACCUM, bool RAW, bool ADAM = false, bool AA = false, bool INVD = false>
 __global__ __launch_bounds__(256) void inria_preprocess_bwd_kernel(
     int N,
     const float* means, const float* scales, const float* quats,
@@ -262,7 +286,10 @@ __global__ __launch_bounds__(256) void inria_preprocess_bwd_kernel(
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (!ADAM && g >= N) return;
     const bool row = g < N;
-    if (ADAM || v_opac_dst) {
+    static_assert(!(ADAM && (AA || INVD)), "the optimizer inside the backward takes neither anti-aliasing nor inverse depth");
+    float aa_g = 0.f, aa_o = 0.f, aa_comp = 1.f;
+    if constexpr (AA) { aa_g = v_opac_src[(int64_t)g * gs2]; aa_o = RAW ? act_sigmoid(opac_act[g]) : opac_act[g]; }
+    if (!AA && (ADAM || v_opac_dst)) {
         float v = row ? v_opac_src[(int64_t)g * gs2] : 0.f;
         if constexpr (RAW) { const float o = row ? opac_act[g] : 0.f; v *= o * (1.f - o); }
         if constexpr (ADAM) s_grad[256 * 10 + threadIdx.x] = v;
@@ -300,8 +327,20 @@ __global__ __launch_bounds__(256) void inria_preprocess_bwd_kernel(
         // conic -> cov2D -> (view-space mean, cov3D)
         float va, vb, vc;
         conic_bwd(G.a, G.b, G.c, v_conics[(int64_t)g * gs3 + 0], v_conics[(int64_t)g * gs3 + 1], v_conics[(int64_t)g * gs3 + 2], va, vb, vc);
+        if constexpr (AA) {
+            // d(det0 / det1) / d(a0, b, c0) with det1 = (a0 + 0.3)(c0 + 0.3) - b^2: ((c0, -2b, a0) - ratio (c, -2b, a)) / det1
+            float ratio;
+            aa_comp = aa_compensation(G, ratio);
+            if (ratio > 2.5e-5f) {
+                const float k = aa_g * aa_o * 0.5f / aa_comp / G.det;      // v_comp d comp / d ratio / det1
+                va += k * (G.c0 - ratio * G.c);
+                vc += k * (G.a0 - ratio * G.a);
+                vb += k * 2.f * G.b * (ratio - 1.f);
+            }
+        }
         float vpv[3] = {0.f, 0.f, 0.f};
         ewa_bwd<false>(G.pv, S6, G.Wstd, G.fx, G.fy, G.ctx, va, vb, vc, vpv, G6);
+        if constexpr (INVD) vpv[2] -= v_means2d[(int64_t)g * gs2 + 9] / (G.pv[2] * G.pv[2]);      // the packed row's 10th column: v(1 / z)
 #pragma unroll
         for (int r = 0; r < 3; ++r) vp[r] += cam.V[r * 4 + 0] * vpv[0] + cam.V[r * 4 + 1] * vpv[1] + cam.V[r * 4 + 2] * vpv[2];
 
@@ -349,6 +388,11 @@ __global__ __launch_bounds__(256) void inria_preprocess_bwd_kernel(
         pre_adam_pass(adam.opac, (int64_t)n0, rows, s_grad + 256 * 10);
         return;
     }
+    if constexpr (AA) {
+        float v = aa_g * aa_comp;
+        if constexpr (RAW) v *= aa_o * (1.f - aa_o);
+        v_opac_dst[g] = v;
+    }
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         if (ACCUM) v_means[g * 3 + j] += vp[j];
@@ -380,23 +424,45 @@ __global__ __launch_bounds__(256) void masked_copy3_kernel(int N, const int32_t*
     }
 }
 
+// GSPL_INRIA_INVDEPTH: the [N,4] rows the compositing kernels read, colour | 1 / z (0 for a culled row: it is in no list)
+__global__ __launch_bounds__(256) void invdepth_rows_kernel(int N, const int32_t* __restrict__ radii, const float* __restrict__ colors3,
+                                                            const float* __restrict__ depths, float4* __restrict__ colors4) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= N) return;
+    const bool live = radii[g] > 0;
+    colors4[g] = make_float4(colors3[g * 3 + 0], colors3[g * 3 + 1], colors3[g * 3 + 2], live ? 1.f / depths[g] : 0.f);
+}
+
+int inria_invdepth_rows_launch(int N, const int32_t* radii, const float* colors3, const float* depths, float* colors4, hipStream_t s) {
+    if (N <= 0) return GSPL_OK;
+    hipLaunchKernelGGL(invdepth_rows_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, radii, colors3, depths, reinterpret_cast<float4*>(colors4));
+    return check_launch("inria_invdepth_rows");
+}
+
 // geometry phase, activated parameters (raw_opacities == NULL) or the model's raw ones (-> opacities_out [N] = sigmoid)
 int inria_geometry_launch(int N, const float* means, const float* scales, const float* quats, const float* cov3d_precomp,
                           const float* viewmatrix, const float* projmatrix, int width, int height, int tile_size,
                           float tanfovx, float tanfovy, float scale_modifier,
                           int32_t* radii, float* means2d, float* depths, float* conics, float* cov3d,
-                          const float* raw_opacities, float* opacities_out, hipStream_t s, ZeroJob zero) {
+                          const float* raw_opacities, float* opacities_out, hipStream_t s, ZeroJob zero, int ext) {
     const int grid = (N + 255) / 256;
-    if (raw_opacities) {
+#define GSPL_LAUNCH_PRE_FWD(R, AAF, OPIN, OPOUT) hipLaunchKernelGGL((inria_preprocess_fwd_kernel<R, AAF>), dim3(grid), dim3(256), 0, s, \
+        N, means, scales, quats, cov3d_precomp, viewmatrix, projmatrix, width, height, tile_size, \
+        tanfovx, tanfovy, scale_modifier, radii, means2d, depths, conics, cov3d, OPIN, OPOUT, zero.p, zero.n16)
+    const bool raw = (ext & GSPL_INRIA_RAW_PARAMS) != 0 || (!(ext & GSPL_INRIA_ANTIALIAS) && raw_opacities);
+    if (ext & GSPL_INRIA_ANTIALIAS) {
+        // (`raw_opacities`: the caller's opacities, raw with GSPL_INRIA_RAW_PARAMS in `ext`, activated without)
+        if (!raw_opacities || !opacities_out || (raw && cov3d_precomp))
+            return fail_arg("inria_preprocess_fwd(antialias): needs the opacities and room for the effective ones (raw: scales + rotations)");
+        if (raw) GSPL_LAUNCH_PRE_FWD(true, true, raw_opacities, opacities_out);
+        else GSPL_LAUNCH_PRE_FWD(false, true, raw_opacities, opacities_out);
+    } else if (raw_opacities) {
         if (cov3d_precomp || !opacities_out) return fail_arg("inria_preprocess_fwd: raw parameters need scales + rotations and room for the opacities");
-        hipLaunchKernelGGL(inria_preprocess_fwd_kernel<true>, dim3(grid), dim3(256), 0, s,
-                           N, means, scales, quats, cov3d_precomp, viewmatrix, projmatrix, width, height, tile_size,
-                           tanfovx, tanfovy, scale_modifier, radii, means2d, depths, conics, cov3d, raw_opacities, opacities_out, zero.p, zero.n16);
+        GSPL_LAUNCH_PRE_FWD(true, false, raw_opacities, opacities_out);
     } else {
-        hipLaunchKernelGGL(inria_preprocess_fwd_kernel<false>, dim3(grid), dim3(256), 0, s,
-                           N, means, scales, quats, cov3d_precomp, viewmatrix, projmatrix, width, height, tile_size,
-                           tanfovx, tanfovy, scale_modifier, radii, means2d, depths, conics, cov3d, (const float*)nullptr, (float*)nullptr, zero.p, zero.n16);
+        GSPL_LAUNCH_PRE_FWD(false, false, (const float*)nullptr, (float*)nullptr);
     }
+#undef GSPL_LAUNCH_PRE_FWD
     return check_launch("inria_preprocess_fwd");
 }
 
@@ -453,8 +519,14 @@ int inria_preprocess_bwd_impl(int N, int degree, int n_coeffs,
                                          float* v_means, float* v_scales, float* v_quats,
                                          float* v_cov3d_precomp, float* v_shs, float* v_shs_rest, float* v_colors_precomp,
                                          float* v_means2d_ndc, const float* v_opacities_packed, float* v_opacities, const float* sh_jac,
-                                         const float* opac_act, void* stream, const gspl_bwd_adam_plan* plan, BwdStats stats) {
+                                         const float* opac_act, void* stream, const gspl_bwd_adam_plan* plan, BwdStats stats, int ext) {
     if (N < 0 || width <= 0 || height <= 0) return fail_arg("inria_preprocess_bwd: bad sizes");
+    // ext: the fused call's GSPL_INRIA_ANTIALIAS / GSPL_INRIA_INVDEPTH bits, and GSPL_INRIA_RAW_PARAMS beside ANTIALIAS (whose `opac_act` is
+    // the caller's opacities, raw or not; without it a non-NULL `opac_act` says RAW, as before)
+    if (ext & ~(GSPL_INRIA_RAW_PARAMS | GSPL_INRIA_ANTIALIAS | GSPL_INRIA_INVDEPTH)) return fail_arg("inria_preprocess_bwd: unknown extension bits");
+    if ((ext & (GSPL_INRIA_ANTIALIAS | GSPL_INRIA_INVDEPTH)) && plan) return fail_arg("inria_preprocess_bwd(adam): neither anti-aliasing nor inverse depth is supported with the optimizer inside the backward");
+    if ((ext & GSPL_INRIA_ANTIALIAS) && (!opac_act || !v_opacities)) return fail_arg("inria_preprocess_bwd(antialias): needs the opacities and v_opacities");
+    if ((ext & GSPL_INRIA_INVDEPTH) && grad_stride < 10) return fail_arg("inria_preprocess_bwd(invdepth): needs the packed rows with the 4th colour column");
     if ((stats.accum == nullptr) != (stats.denom == nullptr) || (stats.max_radii && !stats.accum))
         return fail_arg("inria_preprocess_bwd: the statistics' accum and denom go together (max_radii is optional beside them)");
     if (plan) {
@@ -504,7 +576,9 @@ int inria_preprocess_bwd_impl(int N, int degree, int n_coeffs,
         int rc = check_launch("inria_preprocess_bwd(colors_precomp)");
         if (rc != GSPL_OK) return rc;
     }
-    if (opac_act && (!v_scales || !v_opacities || v_cov3d_precomp)) return fail_arg("inria_preprocess_bwd: raw parameters need v_scales, v_quats and v_opacities");
+    const bool aa = (ext & GSPL_INRIA_ANTIALIAS) != 0, invd = (ext & GSPL_INRIA_INVDEPTH) != 0;
+    const bool raw = aa ? (ext & GSPL_INRIA_RAW_PARAMS) != 0 : opac_act != nullptr;
+    if (raw && (!v_scales || !v_opacities || v_cov3d_precomp)) return fail_arg("inria_preprocess_bwd: raw parameters need v_scales, v_quats and v_opacities");
     PreAdam pre = {};
     if (plan) {
         auto target = [](float* p, const gspl_bwd_adam_tensor& t) {
@@ -515,13 +589,23 @@ int inria_preprocess_bwd_impl(int N, int degree, int n_coeffs,
         pre.quats = target(v_quats, plan->rotations);
         pre.opac = target(v_opacities, plan->opacities);
     }
-#define GSPL_LAUNCH_PRE_BWD(A, R, AD) hipLaunchKernelGGL((inria_preprocess_bwd_kernel<A, R, AD>), dim3(grid), dim3(256), 0, s, \
-        N, means, scales, quats, cov3d, viewmatrix, projmatrix, width, height, tanfovx, tanfovy, scale_modifier, \
-        radii, v_means2d, v_conics, gs2, gs3, v_means, v_scales, v_quats, v_cov3d_precomp, v_means2d_ndc, v_opacities_packed, v_opacities, opac_act, pre, stats)
-    if (plan) { if (opac_act) GSPL_LAUNCH_PRE_BWD(true, true, true); else GSPL_LAUNCH_PRE_BWD(true, false, true); }
+#define GSPL_PRE_BWD_ARGS N, means, scales, quats, cov3d, viewmatrix, projmatrix, width, height, tanfovx, tanfovy, scale_modifier, \
+        radii, v_means2d, v_conics, gs2, gs3, v_means, v_scales, v_quats, v_cov3d_precomp, v_means2d_ndc, v_opacities_packed, v_opacities, opac_act, pre, stats
+#define GSPL_LAUNCH_PRE_BWD(A, R, AD) hipLaunchKernelGGL((inria_preprocess_bwd_kernel<A, R, AD>), dim3(grid), dim3(256), 0, s, GSPL_PRE_BWD_ARGS)
+#define GSPL_LAUNCH_PRE_BWD_EXT(A, R, AAF, INVDF) hipLaunchKernelGGL((inria_preprocess_bwd_kernel<A, R, false, AAF, INVDF>), dim3(grid), dim3(256), 0, s, GSPL_PRE_BWD_ARGS)
+#define GSPL_LAUNCH_PRE_BWD_EXT4(AAF, INVDF) do { \
+        if (accum) { if (raw) GSPL_LAUNCH_PRE_BWD_EXT(true, true, AAF, INVDF); else GSPL_LAUNCH_PRE_BWD_EXT(true, false, AAF, INVDF); } \
+        else { if (raw) GSPL_LAUNCH_PRE_BWD_EXT(false, true, AAF, INVDF); else GSPL_LAUNCH_PRE_BWD_EXT(false, false, AAF, INVDF); } } while (0)
+    if (aa && invd) GSPL_LAUNCH_PRE_BWD_EXT4(true, true);
+    else if (aa) GSPL_LAUNCH_PRE_BWD_EXT4(true, false);
+    else if (invd) GSPL_LAUNCH_PRE_BWD_EXT4(false, true);
+    else if (plan) { if (opac_act) GSPL_LAUNCH_PRE_BWD(true, true, true); else GSPL_LAUNCH_PRE_BWD(true, false, true); }
     else if (accum) { if (opac_act) GSPL_LAUNCH_PRE_BWD(true, true, false); else GSPL_LAUNCH_PRE_BWD(true, false, false); }
     else { if (opac_act) GSPL_LAUNCH_PRE_BWD(false, true, false); else GSPL_LAUNCH_PRE_BWD(false, false, false); }
+#undef GSPL_LAUNCH_PRE_BWD_EXT4
+#undef GSPL_LAUNCH_PRE_BWD_EXT
 #undef GSPL_LAUNCH_PRE_BWD
+#undef GSPL_PRE_BWD_ARGS
     return check_launch("inria_preprocess_bwd");
 }
 }  // namespace gspl
@@ -539,5 +623,5 @@ extern "C" int gspl_inria_preprocess_bwd(int N, int degree, int n_coeffs,
     return gspl::inria_preprocess_bwd_impl(N, degree, n_coeffs, means, scales, quats, cov3d, shs, shs_rest, viewmatrix, projmatrix, campos, width, height,
                                            tanfovx, tanfovy, scale_modifier, radii, clamped, v_means2d, v_conics, v_colors, grad_stride, v_means, v_scales,
                                            v_quats, v_cov3d_precomp, v_shs, v_shs_rest, v_colors_precomp, v_means2d_ndc, v_opacities_packed, v_opacities,
-                                           sh_jac, nullptr, stream, nullptr);
+                                           sh_jac, nullptr, stream, nullptr, gspl::BwdStats(), 0);
 }

@@ -32,7 +32,8 @@ from .binning import (isect_tiles, isect_offset_encode, _PendingBins, MAX_ISECTS
 from .compositing import (_CompositeFn, _composite, rasterize_to_pixels, composite_scores, hit_pixel_count, rasterize_to_weights, rasterize_gaussians)
 from .sharded import (unbind_cameras, pack_visible_records, pack_all_records, unpack_visible_records, _PackRecordsFn, _PackAllRecordsFn,
                       _UnpackRecordsFn, _StageCtx, _ShardFrontFn, _ShardExchangeFn, _ShardBackFn, sharded_front, sharded_exchange, sharded_back)
-from .inria import GaussianRasterizationSettings, GaussianRasterizer, _InriaRasterizeFn, _InriaFusedFn, _split_sh
+from .inria import (GaussianRasterizationSettings, GaussianRasterizer, _InriaRasterizeFn, _InriaFusedFn, _split_sh, rasterize_inria_accel,
+                    AccelRasterizationSettings, AccelGaussianRasterizer)
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

@@ -51,6 +51,10 @@ def _split_sh(sh, sh_rest):
 
 
 class _InriaRasterizeFn(torch.autograd.Function):
+    """The stage-by-stage orchestration (GSPL_FUSED_INRIA=0).  It implements the plain rasterizer only: anti-aliasing and the
+    inverse-depth channel (`diff_accel_gaussian_rasterization`, GSPL_INRIA_ANTIALIAS / GSPL_INRIA_INVDEPTH) exist in the fused call
+    alone, and `rasterize_inria_accel` raises NotImplementedError for them here."""
+
     @staticmethod
     @_guarded(1)
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, settings, sh_rest=None):
@@ -193,9 +197,12 @@ def _view(buf: Tensor, ptr: int, shape, dtype) -> Tensor:
 class _InriaFusedFn(torch.autograd.Function):
     @staticmethod
     @_guarded(1)
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, settings, sh_rest=None, raw_params=False):
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, settings, sh_rest=None, raw_params=False,
+                antialias=False, invdepth=False):
         """raw_params: `opacities`, `scales`, `rotations` are the model's RAW parameters; sigmoid / exp / normalize run inside the preprocess
-        kernels (GSPL_INRIA_RAW_PARAMS) and the backward returns the raw parameters' gradients."""
+        kernels (GSPL_INRIA_RAW_PARAMS) and the backward returns the raw parameters' gradients.
+        antialias: the composited opacity is opacity * sqrt(max(2.5e-5, det0 / det1)) (GSPL_INRIA_ANTIALIAS).
+        invdepth: the output is [4,H,W], colour and the composited inverse view-space depth (background 0; GSPL_INRIA_INVDEPTH)."""
         import ctypes
         s: GaussianRasterizationSettings = settings
         dev = means3D.device
@@ -206,7 +213,10 @@ class _InriaFusedFn(torch.autograd.Function):
         opac = _f32c(opacities).reshape(-1)
         viewm, projm, campos, bg = _f32c(s.viewmatrix), _f32c(s.projmatrix), _f32c(s.campos), _f32c(s.bg)
         sh, sh_rest, n_coeffs = _split_sh(sh, sh_rest)
-        out = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+        D = 4 if invdepth else 3
+        if invdepth:      # the inverse-depth channel's background is 0
+            bg = torch.cat([bg.reshape(-1)[:3], bg.new_zeros(1)])
+        out = torch.empty((D, H, W), dtype=torch.float32, device=dev)
         radii = torch.empty((N,), dtype=torch.int32, device=dev)
         tile_w, tile_h = (W + 15) // 16, (H + 15) // 16
         key = (dev.index, tile_w, tile_h)
@@ -215,6 +225,7 @@ class _InriaFusedFn(torch.autograd.Function):
         will_backward = any(ctx.needs_input_grad)
         state.flags = (L.GSPL_INRIA_RAW_PARAMS if raw_params else 0) | ((L.GSPL_INRIA_FORCE_SEGMENTS if S.segmented_backward == "always" else 0)
                        if (S.segmented_backward and will_backward) else L.GSPL_INRIA_NO_SEGMENTS)      # (only a frame that can have a backward)
+        state.flags |= (L.GSPL_INRIA_ANTIALIAS if antialias else 0) | (L.GSPL_INRIA_INVDEPTH if invdepth else 0)
         if will_backward:
             state.flags |= L.GSPL_INRIA_WILL_BACKWARD      # the forward's compositing kernel clears the backward's packed rows (no fill command there)
         holder = {"device": dev}
@@ -274,7 +285,7 @@ class _InriaFusedFn(torch.autograd.Function):
         # (the error slot must not outlive the call: an allocation the library handled gracefully — checkpoints it can do without — is not an error)
         holder.pop("error", None)
         ctx.cfg = (H, W, int(s.sh_degree), n_coeffs, float(s.tanfovx), float(s.tanfovy), float(s.scale_modifier), colors_precomp is not None,
-                   cov3D_precomp is not None, opacities.shape)
+                   cov3D_precomp is not None, opacities.shape, D)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(radii)
         ctx.means2D_ref = means2D
@@ -284,8 +295,8 @@ class _InriaFusedFn(torch.autograd.Function):
             nI = int(state.n_isects)
             S.last_raster = dict(mode=L.GSPL_MODE_INRIA, width=W, height=H, means2d=_view(geom, state.means2d, (N, 2), torch.float32),
                                conics=_view(geom, state.conics, (N, 3), torch.float32),
-                               opacities=(_view(geom, state.opacities, (N,), torch.float32) if raw_params else opac),
-                               colors=_view(geom, state.colors, (N, 3), torch.float32),
+                               opacities=(_view(geom, state.opacities, (N,), torch.float32) if (raw_params or antialias) else opac),
+                               colors=_view(geom, state.colors, (N, D), torch.float32),
                                flatten_ids=(lists[:4 * nI].view(torch.int32) if lists is not None else torch.empty(0, dtype=torch.int32, device=dev)),
                                offsets=_view(img, state.offsets, (tile_w * tile_h,), torch.int32), radii=radii,
                                depths=_view(geom, state.depths, (N,), torch.float32),
@@ -300,7 +311,8 @@ class _InriaFusedFn(torch.autograd.Function):
     def backward(ctx, v_out, _v_radii):
         import ctypes
         means3D, scales, rotations, sh, opac, viewm, projm, campos, bg, radii, sh_rest, *frame_buffers = ctx.saved_tensors      # (a released graph raises here)
-        H, W, degree, n_coeffs, tanfovx, tanfovy, scale_modifier, has_precomp_colors, use_cov, opac_shape = ctx.cfg
+        H, W, degree, n_coeffs, tanfovx, tanfovy, scale_modifier, has_precomp_colors, use_cov, opac_shape, D = ctx.cfg
+        prow = 6 + D      # the packed row: x y | a b c | opacity | colour (| 1/z)
         N = means3D.shape[0]
         dev = means3D.device
         ctx.backwards_run += 1
@@ -309,17 +321,17 @@ class _InriaFusedFn(torch.autograd.Function):
             for t in frame_buffers:
                 if t.data_ptr() <= ctx.state.seg_words < t.data_ptr() + t.numel():
                     _view(t.data, ctx.state.seg_words, (2,), torch.int32).zero_()      # (.data: the saved tensor's version counter must not move)
-        v_out = _grad_or_zeros(v_out, (3, H, W), dev)
+        v_out = _grad_or_zeros(v_out, (D, H, W), dev)
         E = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         packed = None
         if ctx.packed_at:      # the block the forward's compositing kernel cleared (GSPL_INRIA_PACKED_READY): the C side clears nothing
             for t in frame_buffers:
                 if t.data_ptr() == ctx.packed_at:
-                    packed = _view(t.data, ctx.packed_at, (N, 9), torch.float32)
+                    packed = _view(t.data, ctx.packed_at, (N, prow), torch.float32)
                     if ctx.backwards_run > 1:
                         packed.zero_()      # retain_graph: the rows hold the first backward's sums
         if packed is None:
-            packed = E(N, 9)
+            packed = E(N, prow)
             if ctx.packed_at:
                 raise RuntimeError("GaussianRasterizer: the forward's packed block is gone")
         hit = torch.empty((N,), dtype=torch.uint8, device=dev) if S.track_hit_pixels else None
@@ -334,7 +346,9 @@ class _InriaFusedFn(torch.autograd.Function):
             stats = None
         # An optimizer built with fuse_into_backward=True that owns EVERY parameter differentiated here: the kernels that end the
         # backward apply its update themselves (gspl_rasterize_inria_bwd_adam) and no parameter gradient is written or returned
-        if S.backward_optimizers and N > 0 and not use_cov and not has_precomp_colors:
+        # (not for a frame with anti-aliasing or inverse depth: gspl_rasterize_inria_bwd_adam refuses them, the optimizer then steps itself)
+        extended = bool(ctx.state.flags & (L.GSPL_INRIA_ANTIALIAS | L.GSPL_INRIA_INVDEPTH))
+        if S.backward_optimizers and N > 0 and not use_cov and not has_precomp_colors and not extended:
             need = ctx.needs_input_grad
             if need[0] and need[2] and need[4] and need[5] and need[6] and (sh_rest is None or need[9]):
                 from ..optimizers import claim_backward_update
@@ -355,7 +369,7 @@ class _InriaFusedFn(torch.autograd.Function):
                         ctx.state.stats_accum = ctx.state.stats_denom = ctx.state.stats_max_radii = None
                     if hit is not None and ctx.means2D_ref is not None:
                         ctx.means2D_ref.has_hit_any_pixels = hit.view(torch.bool)
-                    return None, v_ndc, None, None, None, None, None, None, None, None, None
+                    return None, v_ndc, None, None, None, None, None, None, None, None, None, None, None
         v_means, v_ndc, v_opac = E(N, 3), E(N, 3), E(N)
         v_scales = None if use_cov else E(N, 3)
         v_quats = None if use_cov else E(N, 4)
@@ -384,7 +398,7 @@ class _InriaFusedFn(torch.autograd.Function):
         else:
             for t in (v_means, v_ndc, v_opac):
                 t.zero_()
-        return v_means, v_ndc, v_sh, v_cp, v_opac.reshape(opac_shape), v_scales, v_quats, v_cov, None, v_sh_rest, None
+        return v_means, v_ndc, v_sh, v_cp, v_opac.reshape(opac_shape), v_scales, v_quats, v_cov, None, v_sh_rest, None, None, None
 
 
 def _poison(ctx, stats):
@@ -438,3 +452,76 @@ class GaussianRasterizer(torch.nn.Module):
             opacities, scales, rotations = torch.sigmoid(opacities), torch.exp(scales), torch.nn.functional.normalize(rotations)
         out = fn.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, self.raster_settings, shs_rest)
         return _mark_fused(out) if fn is _InriaFusedFn else out
+
+
+def rasterize_inria_accel(settings: GaussianRasterizationSettings, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
+                          rotations=None, cov3D_precomp=None, shs_rest=None, raw_parameters: bool = False, antialiasing: bool = False,
+                          inverse_depth: bool = True):
+    """The fused Inria call with the two switches of `diff_accel_gaussian_rasterization` (Taming 3DGS): `antialiasing` (the Mip-Splatting
+    2D filter, GSPL_INRIA_ANTIALIAS) and `inverse_depth` (a 4th composited channel 1 / z, GSPL_INRIA_INVDEPTH).  Returns (color [3,H,W],
+    radii [N] i32, inverse depth [1,H,W] or None); the two images are views of one [4,H,W] output.  Arguments as `GaussianRasterizer`.
+    There is no stage-by-stage form of these switches: with GSPL_FUSED_INRIA=0 they raise NotImplementedError."""
+    if (shs is None) == (colors_precomp is None):
+        raise Exception("Please provide excatly one of either SHs or precomputed colors!")
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+            ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+        raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+    if not S.fused_inria:
+        if antialiasing or inverse_depth:
+            raise NotImplementedError("anti-aliasing and inverse depth exist in the fused Inria call only (GSPL_FUSED_INRIA=0 selects the staged one)")
+        out, radii = GaussianRasterizer(settings)(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp,
+                                                  shs_rest=shs_rest, raw_parameters=raw_parameters)
+        return out, radii, None
+    if raw_parameters and cov3D_precomp is not None:
+        raise Exception("raw_parameters needs the scale/rotation pair")
+    if shs_rest is not None and shs_rest.shape[1] == 0:
+        shs_rest = None
+    out, radii = _mark_fused(_InriaFusedFn.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, settings,
+                                                 shs_rest, bool(raw_parameters), bool(antialiasing), bool(inverse_depth)))
+    if inverse_depth:
+        return out[:3], radii, out[3:]
+    return out, radii, None
+
+
+# ---- diff_accel_gaussian_rasterization (the Taming 3DGS rasterizer package, internal/renderers/taming_3dgs_renderer.py:4) -------------
+class AccelRasterizationSettings(NamedTuple):
+    """`diff_accel_gaussian_rasterization.GaussianRasterizationSettings`: the Inria fields and `antialiasing`."""
+    image_height: int
+    image_width: int
+    tanfovx: float
+    tanfovy: float
+    bg: Tensor
+    scale_modifier: float
+    viewmatrix: Tensor
+    projmatrix: Tensor
+    sh_degree: int
+    campos: Tensor
+    prefiltered: bool = False
+    debug: bool = False
+    antialiasing: bool = False
+
+
+class AccelGaussianRasterizer(torch.nn.Module):
+    """Drop-in for `diff_accel_gaussian_rasterization.GaussianRasterizer` as the reference calls it
+    (internal/renderers/taming_3dgs_renderer.py:66-96): returns (color [3,H,W], radii [N] i32, inverse depth [1,H,W]).  `dc` [N,1,3] and
+    `shs` [N,K-1,3] are the two SH parameters (read in place as `shs` / `shs_rest`); `means2D.grad` receives the same NDC-scaled
+    screen-space gradient as `GaussianRasterizer`'s.  Runs the fused call with GSPL_INRIA_INVDEPTH (and GSPL_INRIA_ANTIALIAS when the
+    settings ask for it)."""
+
+    def __init__(self, raster_settings: AccelRasterizationSettings):
+        super().__init__()
+        self.raster_settings = raster_settings
+
+    def forward(self, means3D, means2D, dc=None, shs=None, colors_precomp=None, opacities=None, scales=None, rotations=None, cov3D_precomp=None,
+                raw_parameters: bool = False):
+        if colors_precomp is None and dc is None and shs is None:
+            raise Exception("Please provide excatly one of either SHs or precomputed colors!")
+        if colors_precomp is not None:
+            sh, sh_rest = None, None
+        elif dc is None:
+            sh, sh_rest = shs, None
+        else:
+            sh, sh_rest = dc, shs
+        return rasterize_inria_accel(self.raster_settings, means3D, means2D, opacities, sh, colors_precomp, scales, rotations, cov3D_precomp,
+                                     shs_rest=sh_rest, raw_parameters=raw_parameters,
+                                     antialiasing=bool(getattr(self.raster_settings, "antialiasing", False)), inverse_depth=True)

@@ -323,6 +323,33 @@ class SelectiveAdam(_FusedAdamBase):
         self._launch(visibility)
 
 
+class _AdamOptimizerInit(torch.optim.Adam):
+    """Puts `torch.optim.Adam` into a fused optimizer's bases (isinstance checks, `__setstate__`) while the construction stays
+    `torch.optim.Optimizer`'s: `_FusedAdamBase.__init__` hands it (params, defaults)."""
+
+    def __init__(self, params, defaults):
+        torch.optim.Optimizer.__init__(self, params, defaults)
+
+
+class SparseGaussianAdam(_FusedAdamBase, _AdamOptimizerInit):
+    """`diff_accel_gaussian_rasterization.SparseGaussianAdam(params, lr, eps)` (Taming 3DGS; internal/optimizers.py:63-90): Adam without
+    bias correction, betas (0.9, 0.999), applied only to the rows whose `visibility` is set — `step(visibility, N)`.  The arithmetic of
+    `SelectiveAdam` (one masked launch); a `torch.optim.Adam` by type, with its state keys (step / exp_avg / exp_avg_sq), so that
+    `torch.optim.Adam` checkpoints load and the density controller's state surgery applies."""
+    _bias_correction = False
+
+    def __init__(self, params, lr: float = 1e-3, eps: float = 1e-8, **kwargs):
+        super().__init__(params, lr=lr, betas=(0.9, 0.999), eps=eps, **kwargs)
+        for k, v in (("amsgrad", False), ("maximize", False), ("foreach", None), ("capturable", False), ("differentiable", False), ("fused", None)):
+            self.defaults.setdefault(k, v)      # what torch.optim.Adam's helpers (and the reference's step decorator) look up
+
+    @torch.no_grad()
+    def step(self, visibility: torch.Tensor, N: int = None):
+        if N is not None and visibility.shape[0] != N:
+            raise ValueError(f"SparseGaussianAdam: visibility has {visibility.shape[0]} rows, N = {N}")
+        self._launch(visibility)
+
+
 class FusedAdam(_FusedAdamBase):
     """`torch.optim.Adam` semantics (bias-corrected, every row) for [N, ...] fp32 parameters, one launch per step."""
 
@@ -364,6 +391,32 @@ class HipFusedAdam(_OptimizerConfig):
         if self.fuse_into_backward:
             kwargs.setdefault("fuse_into_backward", True)
         return FusedAdam(params, lr, *args, **kwargs)
+
+
+@dataclass
+class HipSparseGaussianAdam(_OptimizerConfig):
+    """Drop-in for `internal.optimizers.SparseGaussianAdam` (internal/optimizers.py:63-90): visibility = outputs["visibility_filter"]."""
+
+    def instantiate(self, params, lr: float, *args, **kwargs):
+        params = list(params)
+        for group in params:
+            if isinstance(group, dict) and "lr" not in group:
+                group["lr"] = lr
+
+        class Adapter(SparseGaussianAdam):
+            def on_after_backward(self, outputs, batch, gaussian_model, global_step, pl_module):
+                self.visibility = outputs["visibility_filter"]
+
+            @torch.no_grad()
+            def step(self, closure=None):
+                loss = None
+                if closure is not None:
+                    with torch.enable_grad():
+                        loss = closure()
+                SparseGaussianAdam.step(self, self.visibility, self.visibility.shape[0])
+                return loss
+
+        return Adapter(params, lr, *args, **kwargs)
 
 
 @dataclass

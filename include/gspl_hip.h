@@ -398,7 +398,8 @@ typedef struct gspl_inria_state {
     int32_t* flatten_ids;                                                                              /* GSPL_BUF_LISTS */
     float* opacities;      /* GSPL_BUF_GEOMETRY: the opacities compositing read — the caller's tensor, or with GSPL_INRIA_RAW_PARAMS
                               sigmoid(raw) [N] as the forward stored it */
-    int flags;             /* IN (forward; the backward reads it back): 0 — a zeroed struct — or GSPL_INRIA_RAW_PARAMS | GSPL_INRIA_NO_SEGMENTS */
+    int flags;             /* IN (forward; the backward reads it back): 0 — a zeroed struct — or GSPL_INRIA_RAW_PARAMS | GSPL_INRIA_NO_SEGMENTS
+                              | GSPL_INRIA_ANTIALIAS | GSPL_INRIA_INVDEPTH ... (below) */
     /* segmented backward (ABI 33): per-pixel checkpoints the forward left every 256 list entries and the words
      * [count | - | work items seg_slots] in front of them (one GSPL_BUF_CHECKPOINTS block); seg_ckpt == NULL: this frame is not segmented */
     void* seg_ckpt; uint32_t* seg_words; uint32_t seg_slots; uint32_t seg_reserved;
@@ -420,8 +421,22 @@ enum { GSPL_INRIA_RAW_PARAMS = 1,
                                        kernel (VALU-bound, the memory system idle) clears it, instead of a 7 us fill command in front of the
                                        backward's first kernel */,
        GSPL_INRIA_PACKED_READY = 16 /* OUT (set by the forward in state->flags): the GSPL_BUF_PACKED block is cleared and the backward will NOT
-                                       clear its `packed` argument — which must be that block */ };
-size_t gspl_rasterize_inria_geometry_bytes(int N);
+                                       clear its `packed` argument — which must be that block */,
+       GSPL_INRIA_ANTIALIAS = 32 /* ABI 36, IN: the Mip-Splatting 2D filter (graphdeco `dr_aa` / Taming 3DGS `antialiasing=True`): the
+                                    opacity compositing and the binning read is opacity * comp, comp = sqrt(max(2.5e-5, det0 / det1)) with
+                                    det0 / det1 the determinant of the 2D covariance before / after its +0.3 dilation; state->opacities
+                                    then always holds those effective opacities [N] (activated first with GSPL_INRIA_RAW_PARAMS) and the
+                                    backward chains the compensation into the covariance.  Radii and conics are unchanged */,
+       GSPL_INRIA_INVDEPTH = 128 /* ABI 36, IN: a 4th composited channel, 1 / z of the view-space depth (background 0): out_color is
+                                   [4,H,W] (colour | inverse depth), `bg` holds FOUR values (the caller's 3 and a 0), state->colors is
+                                   [N,4], GSPL_BUF_PACKED is 40 N bytes (rounded up to 16) and the backward's `packed` [N,10]
+                                   (x y | a b c | opacity | r g b | 1/z) and v_out_color [4,H,W].  The segmented backward carries the
+                                   4th channel: GSPL_BUF_CHECKPOINTS grows by one float per checkpoint (5 KB per 256 list entries of
+                                   capacity), and GSPL_INRIA_FORCE_SEGMENTS / NO_SEGMENTS mean what they mean without it.  Neither this
+                                   bit nor GSPL_INRIA_ANTIALIAS is accepted by gspl_rasterize_inria_bwd_adam.  (Bit 64 stays unused:
+                                   callers have used it as the example of an unknown bit the forward refuses.) */ };
+size_t gspl_rasterize_inria_geometry_bytes(int N);      /* the GSPL_BUF_GEOMETRY request of a frame WITHOUT GSPL_INRIA_INVDEPTH; with it the
+                                                          request is larger (16 N more bytes, rounded up to 256: the [N,4] rows) */
 size_t gspl_rasterize_inria_image_bytes(int width, int height);
 size_t gspl_inria_state_bytes(void);      /* sizeof(gspl_inria_state) as the library was built: a binding checks its own layout against it */
 int gspl_rasterize_inria_fwd(int N, int degree, int n_coeffs,
