@@ -16,7 +16,7 @@ import torch
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSPL_HIP_LIB", os.path.join(_PKG_DIR, "libgspl_hip.so"))   # override: A/B builds of the same ABI
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 GSPL_RECORD_FLOATS = 12
 GSPL_CAMERA_PINHOLE, GSPL_CAMERA_ORTHO, GSPL_CAMERA_FISHEYE = 0, 1, 2
@@ -61,6 +61,7 @@ class HipLibraryError(RuntimeError):
 
 # `gspl_alloc_fn` / `gspl_inria_state` of include/gspl_hip.h (the fused Inria entry points)
 GSPL_BUF_GEOMETRY, GSPL_BUF_BINNING, GSPL_BUF_IMAGE, GSPL_BUF_LISTS_WORK, GSPL_BUF_LISTS, GSPL_BUF_CHECKPOINTS, GSPL_BUF_PACKED = 1, 2, 3, 4, 5, 6, 7
+GSPL_BUF_SURFEL_ENTRIES = 8    # (ABI 37) the deterministic surfel backward's per-list-entry rows
 ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t)
 
 
@@ -72,6 +73,15 @@ class InriaState(ctypes.Structure):
                 ("flatten_ids", ctypes.c_void_p), ("opacities", ctypes.c_void_p), ("flags", ctypes.c_int),
                 ("seg_ckpt", ctypes.c_void_p), ("seg_words", ctypes.c_void_p), ("seg_slots", ctypes.c_uint32), ("seg_reserved", ctypes.c_uint32),
                 ("stats_accum", ctypes.c_void_p), ("stats_denom", ctypes.c_void_p), ("stats_max_radii", ctypes.c_void_p)]
+
+
+class SurfelState(ctypes.Structure):
+    """`gspl_surfel_state` of include/gspl_hip.h (section 6c, the 2DGS rasterizer)."""
+    _fields_ = [("N", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int), ("n_isects", ctypes.c_int64),
+                ("rec", ctypes.c_void_p), ("means2d", ctypes.c_void_p), ("depths", ctypes.c_void_p), ("colors", ctypes.c_void_p),
+                ("clamped", ctypes.c_void_p), ("final_T", ctypes.c_void_p), ("M1", ctypes.c_void_p), ("M2", ctypes.c_void_p),
+                ("last_contrib", ctypes.c_void_p), ("median_contrib", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
+                ("flatten_ids", ctypes.c_void_p)]
 
 
 _P = c_void_p
@@ -153,6 +163,11 @@ _SIGNATURES = {
     "gspl_rasterize_inria_geometry_bytes": (c_size_t, [c_int]),
     "gspl_rasterize_inria_image_bytes": (c_size_t, [c_int, c_int]),
     "gspl_inria_state_bytes": (c_size_t, []),
+    "gspl_surfel_state_bytes": (c_size_t, []),
+    "gspl_rasterize_surfel_fwd": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_float,
+                                          ALLOC_FN, _P, _P, _P, _P, ctypes.POINTER(SurfelState), _P]),
+    "gspl_rasterize_surfel_bwd": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_float, _P, ctypes.POINTER(SurfelState), _P, _P,
+                                          ALLOC_FN, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gspl_inria_preprocess_bwd": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                           c_int, c_int, c_float, c_float, c_float,
                                           _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -205,6 +220,9 @@ def lib():
     if handle.gspl_inria_state_bytes() != ctypes.sizeof(InriaState):
         raise HipLibraryError(f"gspl_inria_state: the library's struct has {handle.gspl_inria_state_bytes()} bytes, the binding's "
                               f"{ctypes.sizeof(InriaState)}; rebuild the extension")
+    if handle.gspl_surfel_state_bytes() != ctypes.sizeof(SurfelState):
+        raise HipLibraryError(f"gspl_surfel_state: the library's struct has {handle.gspl_surfel_state_bytes()} bytes, the binding's "
+                              f"{ctypes.sizeof(SurfelState)}; rebuild the extension")
     _LIB = handle
     return _LIB
 

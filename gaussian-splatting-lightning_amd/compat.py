@@ -1,8 +1,8 @@
 """Import shims for the reference's un-vendored native packages that this package replaces.
 
 Besides the two small helpers below (`simple_knn`, `fused_ssim`), `install()` registers stand-ins for the rasterizer
-packages themselves — `diff_gaussian_rasterization`, Taming 3DGS's `diff_accel_gaussian_rasterization` and the yzslab `gsplat`
-fork — under the module paths and function names the
+packages themselves — `diff_gaussian_rasterization`, Taming 3DGS's `diff_accel_gaussian_rasterization`, 2DGS's
+`diff_surfel_rasterization` and the yzslab `gsplat` fork — under the module paths and function names the
 reference imports (internal/renderers/vanilla_renderer.py:4, gsplat_renderer.py:2-4, gsplat_v1_renderer.py:8-20,
 pypreprocess_gsplat_renderer.py:1-2, gsplat_hit_pixel_count_renderer.py:5, internal/optimizers.py:34 ...), each bound to the HIP
 op of `gspl_amd.ops` with the same signature.  With them the reference's OWN renderer classes (`VanillaRenderer`,
@@ -100,6 +100,12 @@ def _install_rasterizer_packages(installed: list):
                 GaussianRasterizationSettings=ops.AccelRasterizationSettings, GaussianRasterizer=ops.AccelGaussianRasterizer,
                 SparseGaussianAdam=optimizers.SparseGaussianAdam)
         installed.append("diff_accel_gaussian_rasterization")
+    if _missing("diff_surfel_rasterization"):
+        from . import ops
+        _module("diff_surfel_rasterization",
+                "gspl_amd stand-in for diff_surfel_rasterization (2D Gaussian Splatting; HIP: gspl_amd.ops.SurfelGaussianRasterizer)",
+                GaussianRasterizationSettings=ops.SurfelRasterizationSettings, GaussianRasterizer=ops.SurfelGaussianRasterizer)
+        installed.append("diff_surfel_rasterization")
     if _missing("gsplat"):
         doc = "gspl_amd stand-in for the gsplat fork (HIP ops of gspl_amd.ops under the fork's module paths)"
         pkg = _module("gsplat", doc, spherical_harmonics=_late("spherical_harmonics"))

@@ -9,6 +9,8 @@ reference's renderers call (same names, argument meaning and error behaviour):
       project_gaussians, rasterize_gaussians
   Inria (internal/renderers/vanilla_renderer.py:14)
       GaussianRasterizationSettings, GaussianRasterizer
+  2DGS surfels (internal/renderers/vanilla_2dgs_renderer.py:14, `diff_surfel_rasterization`)
+      SurfelRasterizationSettings, SurfelGaussianRasterizer
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -34,6 +36,7 @@ from .sharded import (unbind_cameras, pack_visible_records, pack_all_records, un
                       _UnpackRecordsFn, _StageCtx, _ShardFrontFn, _ShardExchangeFn, _ShardBackFn, sharded_front, sharded_exchange, sharded_back)
 from .inria import (GaussianRasterizationSettings, GaussianRasterizer, _InriaRasterizeFn, _InriaFusedFn, _split_sh, rasterize_inria_accel,
                     AccelRasterizationSettings, AccelGaussianRasterizer)
+from .surfel import SurfelRasterizationSettings, SurfelGaussianRasterizer, rasterize_surfels, _SurfelRasterizeFn
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

@@ -17,3 +17,4 @@ from .hip_gsplat_v1_renderer import HipGSplatV1Renderer, HipGSplatV1RendererModu
 from .hip_gsplat_hit_pixel_count_renderer import HipGSplatHitPixelCountRenderer  # noqa: F401,E402
 from .hip_gsplat_distributed_renderer import HipGSplatDistributedRenderer, HipGSplatDistributedRendererImpl  # noqa: F401,E402
 from .hip_taming_3dgs_renderer import HipTaming3DGSRenderer  # noqa: F401,E402
+from .hip_vanilla_2dgs_renderer import HipVanilla2DGSRenderer  # noqa: F401,E402

@@ -489,6 +489,48 @@ int gspl_rasterize_inria_bwd_adam(int degree, int n_coeffs,
                                   float* packed, uint8_t* hit_flags /*nullable*/, float* scratch_means, float* v_means2D_ndc,
                                   const gspl_bwd_adam_plan* plan /* host */, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 6c. The 2D Gaussian Splatting (surfel) rasterizer in one call per direction (ABI 37): what `diff_surfel_rasterization`'s
+ *    native calls are to the reference's `Vanilla2DGSRenderer` (internal/renderers/vanilla_2dgs_renderer.py:50-90).  The rule is the
+ *    published 2DGS rasterizer restated in this library's Inria conventions (csrc/surfel.hip; parity with the CUDA package is
+ *    unpinned, an fp64 oracle pins the restatement): each splat is a disc in the plane of its two scaled tangent axes, each pixel
+ *    intersects its ray with that plane.  Memory comes from `alloc` as in 6b (tags GEOMETRY, IMAGE, BINNING, LISTS_WORK, LISTS; the
+ *    deterministic backward asks for GSPL_BUF_SURFEL_ENTRIES); no hipMalloc, one host read-back of the list length per frame.
+ *      scales [N,2] (the two tangent scales), rotations [N,4] (w,x,y,z; normalised inside), opacities [N]; shs [N,n_coeffs,3] with
+ *      campos, or colors_precomp [N,3]; bg [3].  No precomputed transform (the reference passes cov3D_precomp = None).
+ *    Outputs: out_color [3,H,W] (+ T bg), out_allmap [7,H,W] = depth | alpha | view-space normal (3) | median depth | distortion
+ *             (no background), radii i32 [N] (0 = culled).  `state` receives what the backward needs.
+ *    Backward: the exact derivative with the 0.99 alpha clamp straight-through and no gradient through a clamped SH channel, except
+ *    v_means2D [N,3]: upstream's densification proxy (dL/dTu.z Tw.z W/2, dL/dTv.z Tw.z H/2, 0) from the compositing backward's
+ *    gradient of the splat's transform alone.  v_rows [N,18] f32 is scratch (cleared inside); exactly one of v_shs [N,n_coeffs,3] /
+ *    v_colors_precomp [N,3]; v_scales [N,2], v_rotations [N,4], v_opacities [N], v_means3D [N,3].  gspl_get_deterministic(): the
+ *    per-splat gradients are added up in list order (bit-reproducible).
+ * ---------------------------------------------------------------------------------------- */
+enum { GSPL_BUF_SURFEL_ENTRIES = 8 /* deterministic surfel backward: 72 B per list entry + the id sort's keys and workspace */ };
+typedef struct gspl_surfel_state {
+    int N, width, height;
+    int64_t n_isects;
+    float* rec;            /* [N,16] Tu Tv Tw | centre | opacity | view normal | 0   (GSPL_BUF_GEOMETRY, as the next four) */
+    float* means2d; float* depths; float* colors; uint8_t* clamped;
+    float* final_T; float* M1; float* M2; int32_t* last_contrib; int32_t* median_contrib; int32_t* offsets;      /* GSPL_BUF_IMAGE */
+    int32_t* flatten_ids;                                                                                         /* GSPL_BUF_LISTS */
+} gspl_surfel_state;
+size_t gspl_surfel_state_bytes(void);      /* sizeof(gspl_surfel_state) as the library was built */
+int gspl_rasterize_surfel_fwd(int N, int degree, int n_coeffs,
+                              const float* means3D, const float* scales, const float* rotations,
+                              const float* shs /*nullable*/, const float* colors_precomp /*nullable*/, const float* opacities,
+                              const float* viewmatrix, const float* projmatrix, const float* campos, const float* bg,
+                              int width, int height, float scale_modifier,
+                              gspl_alloc_fn alloc, void* alloc_ctx,
+                              float* out_color, float* out_allmap, int32_t* radii, gspl_surfel_state* state, void* stream);
+int gspl_rasterize_surfel_bwd(int degree, int n_coeffs,
+                              const float* means3D, const float* scales, const float* rotations, const float* shs /*nullable*/,
+                              const float* viewmatrix, const float* projmatrix, const float* campos, const float* bg, float scale_modifier,
+                              const int32_t* radii, const gspl_surfel_state* state, const float* v_out_color, const float* v_out_allmap,
+                              gspl_alloc_fn alloc /*nullable outside the deterministic mode*/, void* alloc_ctx, float* v_rows,
+                              float* v_means3D, float* v_means2D, float* v_shs /*nullable*/, float* v_colors_precomp /*nullable*/,
+                              float* v_opacities, float* v_scales, float* v_rotations, void* stream);
+
 /* A per-device stream of the LOWEST priority the device offers, created on first use and kept: a `side_stream` for
  * gspl_rasterize_inria_fwd whose colour kernel then yields to the kernels on the caller's stream.  NULL on failure. */
 void* gspl_low_priority_stream(void);

@@ -1,0 +1,131 @@
+"""Step time of the 2DGS (surfel) rasterizer against the fused Inria step, on bench.py's metric workload (S-1080p-1M, the heterogeneous
+16-camera set, one camera per step).  Variants, alternated round by round inside ONE process so that clock and thermal drift spread over
+both:
+
+  vanilla   GaussianRasterizer (raw parameters, shs / shs_rest) + FusedAdam, the L1 + SSIM loss
+  surfel    HipVanilla2DGSRenderer forward, the L1 + SSIM loss plus GS2D's normal-consistency and distortion terms, backward, and Adam
+            (FusedAdam over the activated parameters: the 2DGS renderer takes the model's activated values)
+
+Prints one JSON line: per variant the median over rounds of the mean step time (ms) and the surfel / vanilla ratio.
+  python tools/surfel_step_time.py [--workload S-1080p-1M] [--rounds 5] [--steps 30] [--warmup 8] [--variants vanilla,surfel]
+Under `rocprofv3 --kernel-trace --stats -- python tools/surfel_step_time.py --variants surfel --rounds 1` it gives per-kernel figures."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+VARIANTS = ("vanilla", "surfel")
+
+
+class _Camera:
+    """The fields of the reference's Camera the renderers read (internal/cameras/cameras.py)."""
+
+    def __init__(self, cam, dev):
+        import math
+        self.world_to_camera, self.full_projection, self.camera_center = cam["world_to_camera"], cam["full_projection"], cam["camera_center"]
+        self.width = torch.tensor(cam["width"], dtype=torch.int32, device=dev)
+        self.height = torch.tensor(cam["height"], dtype=torch.int32, device=dev)
+        self.fov_x = torch.tensor(2 * math.atan(cam["tanfovx"]), device=dev)
+        self.fov_y = torch.tensor(2 * math.atan(cam["tanfovy"]), device=dev)
+
+
+class _SurfelModel:
+    """Activated 2DGS parameters in the getters `Vanilla2DGSRenderer` reads (internal/models/gaussian_2d.py)."""
+
+    def __init__(self, params):
+        self.params = params
+        self.active_sh_degree = 3
+
+    get_xyz = property(lambda s: s.params[0])
+    get_scaling = property(lambda s: s.params[1])
+    get_rotation = property(lambda s: s.params[2])
+    get_opacity = property(lambda s: s.params[3])
+    get_features = property(lambda s: s.params[4])
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--workload", default="S-1080p-1M")
+    p.add_argument("--rounds", type=int, default=5)
+    p.add_argument("--steps", type=int, default=30)
+    p.add_argument("--warmup", type=int, default=8)
+    p.add_argument("--variants", default=",".join(VARIANTS))
+    a = p.parse_args()
+    import gspl_amd  # noqa: F401
+    from gspl_amd import ops, optimizers, synthetic
+    from gspl_amd.renderers import HipVanilla2DGSRenderer
+    variants = [v for v in a.variants.split(",") if v]
+    assert all(v in VARIANTS for v in variants), variants
+    dev = torch.device("cuda:0")
+    wl = synthetic.WORKLOADS[a.workload]
+    W, H = wl["width"], wl["height"]
+    means, scales, quats, opac, shs = [t.to(dev) for t in synthetic.workload_scene(wl, seed=42)]
+    cams = synthetic.camera_set(W, H, wl["fx"], count=16, distance=wl.get("distance", 4.0))
+    cams = [{k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in c.items()} for c in cams]
+    rcams = [_Camera(c, dev) for c in cams]
+    bg = torch.zeros(3, device=dev)
+    gen = torch.Generator(device=dev).manual_seed(7)
+    target = torch.rand(3, H, W, device=dev, generator=gen)
+    renderer = HipVanilla2DGSRenderer(depth_ratio=0.0)
+
+    def make(variant):
+        if variant == "vanilla":
+            params = [torch.nn.Parameter(t.clone()) for t in (means, scales.log(), quats, torch.logit(opac.clamp(1e-4, 1 - 1e-4)),
+                                                             shs[:, :1].contiguous(), shs[:, 1:].contiguous())]
+        else:
+            params = [torch.nn.Parameter(t.clone()) for t in (means, scales, quats, opac, shs)]
+        groups = [{"params": [q], "name": str(i)} for i, q in enumerate(params)]
+        return params, optimizers.FusedAdam(groups, lr=1e-4)
+
+    def step(variant, params, opt, ci):
+        cam = cams[ci]
+        if variant == "vanilla":
+            m, s, q, o, dc, rest = params
+            st = ops.GaussianRasterizationSettings(H, W, cam["tanfovx"], cam["tanfovy"], bg, 1.0, cam["world_to_camera"], cam["full_projection"], 3,
+                                                   cam["camera_center"])
+            screen = torch.empty_like(m).requires_grad_(True)
+            img, _ = ops.GaussianRasterizer(st)(m, screen, o, shs=dc, shs_rest=rest, scales=s, rotations=q, raw_parameters=True)
+            l1, ssim = ops.l1_ssim(img, target)
+            loss = 0.8 * l1 + 0.2 * (1 - ssim)
+        else:
+            out = renderer(rcams[ci], _SurfelModel(params), bg)
+            l1, ssim = ops.l1_ssim(out["render"], target)
+            normal_error = (1 - (out["rend_normal"] * out["surf_normal"]).sum(dim=0))[None]
+            loss = 0.8 * l1 + 0.2 * (1 - ssim) + 0.05 * normal_error.mean() + 100.0 * out["rend_dist"].mean()
+        loss.backward()
+        opt.step()
+        opt.zero_grad(set_to_none=True)
+
+    state = {v: make(v) for v in variants}
+    order = [int(i) for i in synthetic.epoch_order(len(cams), 0)]
+    times = {v: [] for v in variants}
+    k = 0
+    for r in range(a.rounds):
+        for v in (variants if r % 2 == 0 else variants[::-1]):
+            params, opt = state[v]
+            for i in range(a.warmup):
+                step(v, params, opt, order[(k + i) % len(order)])
+            torch.cuda.synchronize()
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for i in range(a.steps):
+                step(v, params, opt, order[(k + i) % len(order)])
+            t1.record()
+            torch.cuda.synchronize()
+            times[v].append(t0.elapsed_time(t1) / a.steps)
+        k += a.steps
+    med = {v: statistics.median(times[v]) for v in variants}
+    print(json.dumps({"workload": a.workload, "cameras": "heterogeneous x16", "rounds": a.rounds, "steps": a.steps,
+                      "ms_per_step_median": {v: round(med[v], 4) for v in variants},
+                      "ms_per_step_rounds": {v: [round(x, 4) for x in times[v]] for v in variants},
+                      "ratio_surfel_to_vanilla": (round(med["surfel"] / med["vanilla"], 4) if len(med) == 2 else None)}))
+
+
+if __name__ == "__main__":
+    main()
