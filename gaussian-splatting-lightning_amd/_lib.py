@@ -16,7 +16,7 @@ import torch
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSPL_HIP_LIB", os.path.join(_PKG_DIR, "libgspl_hip.so"))   # override: A/B builds of the same ABI
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 GSPL_RECORD_FLOATS = 12
 GSPL_CAMERA_PINHOLE, GSPL_CAMERA_ORTHO, GSPL_CAMERA_FISHEYE = 0, 1, 2
@@ -171,6 +171,13 @@ _SIGNATURES = {
     "gspl_inria_preprocess_bwd": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                           c_int, c_int, c_float, c_float, c_float,
                                           _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # section 13 (ABI 38): the 3DGS-MCMC density controller (csrc/mcmc.hip)
+    "gspl_mcmc_relocation": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "gspl_mcmc_perturb_means": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_float, ctypes.c_uint64, ctypes.c_uint64, _P]),
+    "gspl_mcmc_randn": (c_int, [c_int, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P]),
+    "gspl_mcmc_reg_partials": (c_int, [c_int]),
+    "gspl_mcmc_reg_fwd": (c_int, [c_int, c_int, _P, _P, c_float, c_float, _P, _P, _P]),
+    "gspl_mcmc_reg_bwd": (c_int, [c_int, c_int, _P, _P, c_float, c_float, _P, _P, _P, _P]),
 }
 
 _LIB = None

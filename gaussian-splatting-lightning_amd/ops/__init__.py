@@ -11,6 +11,8 @@ reference's renderers call (same names, argument meaning and error behaviour):
       GaussianRasterizationSettings, GaussianRasterizer
   2DGS surfels (internal/renderers/vanilla_2dgs_renderer.py:14, `diff_surfel_rasterization`)
       SurfelRasterizationSettings, SurfelGaussianRasterizer
+  3DGS-MCMC (internal/density_controllers/mcmc_density_controller.py:13, `gsplat.relocation`; not registered in compat)
+      compute_relocation, perturb_means_, mcmc_regularization
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -37,6 +39,7 @@ from .sharded import (unbind_cameras, pack_visible_records, pack_all_records, un
 from .inria import (GaussianRasterizationSettings, GaussianRasterizer, _InriaRasterizeFn, _InriaFusedFn, _split_sh, rasterize_inria_accel,
                     AccelRasterizationSettings, AccelGaussianRasterizer)
 from .surfel import SurfelRasterizationSettings, SurfelGaussianRasterizer, rasterize_surfels, _SurfelRasterizeFn
+from .mcmc import compute_relocation, perturb_means_, mcmc_regularization, mcmc_randn, _MCMCRegFn
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

@@ -63,3 +63,38 @@ def replace_tensors_to_properties(tensors: Dict[str, torch.Tensor], optimizers, 
     except Exception:
         return _swap_parameters(tensors, optimizers, selector)
     return Utils.replace_tensors_to_properties(tensors, optimizers, selector)
+
+
+def _cat_parameters(new_properties: Dict[str, torch.Tensor], model, optimizers: List[torch.optim.Optimizer]) -> Dict[str, torch.nn.Parameter]:
+    """Rows appended: a name an optimizer trains gets `cat(old, new)` as a fresh Parameter in its group, its moments grow by zero rows;
+    every other name becomes a frozen Parameter of the concatenation (what the reference's `Utils.cat_tensors_to_properties` does,
+    internal/density_controllers/density_controller.py:46-103)."""
+    index = _groups_by_name(optimizers)
+    out: Dict[str, torch.nn.Parameter] = {}
+    for name, extension in new_properties.items():
+        owner = index.get(name)
+        if owner is None:
+            out[name] = torch.nn.Parameter(torch.cat([model.get_property(name), extension], dim=0), requires_grad=False)
+            continue
+        optimizer, group = owner
+        if len(group["params"]) != 1:
+            raise ValueError(f"optimizer group {name!r} holds {len(group['params'])} parameters, expected one")
+        previous = group["params"][0]
+        fresh = torch.nn.Parameter(torch.cat((previous, extension), dim=0).requires_grad_(True))
+        state = optimizer.state.pop(previous, None)
+        if state is not None:
+            for key in ("exp_avg", "exp_avg_sq"):
+                if key in state:
+                    state[key] = torch.cat((state[key], torch.zeros_like(extension)), dim=0)
+            optimizer.state[fresh] = state
+        group["params"][0] = fresh
+        out[name] = fresh
+    return out
+
+
+def cat_tensors_to_properties(new_properties: Dict[str, torch.Tensor], model, optimizers) -> Dict[str, torch.Tensor]:
+    try:  # pragma: no cover - only inside the reference repo (needs lightning)
+        from internal.density_controllers.density_controller import Utils  # type: ignore
+    except Exception:
+        return _cat_parameters(new_properties, model, optimizers)
+    return Utils.cat_tensors_to_properties(new_properties, model, optimizers)

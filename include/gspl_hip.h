@@ -747,6 +747,45 @@ int gspl_composite_scores(int N, int64_t n_isects, int mode,
                           int32_t* count, float* opacity_sum, float* alpha_sum, float* visibility_sum,
                           float* weighted_sum, float* dist_sum, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 13. The 3DGS-MCMC density controller's per-step math (ABI 38; csrc/mcmc.hip): what `gsplat.relocation.compute_relocation`
+ *    and the PyTorch lines of `MCMCDensityControllerImpl._add_xyz_noise` (internal/density_controllers/
+ *    mcmc_density_controller.py:93-119) and `MCMCMetricsModuleMixin.reg_loss` (internal/metrics/mcmc_metrics.py) compute.
+ *
+ *  gspl_mcmc_relocation: per row m, n = clamp(ratios[m], 1, n_max), o = opacities[m] (activated), Eq. 9 of Kheradmand et al.:
+ *        x = 1 - (1 - o)^(1/n)     (evaluated as -expm1(log1p(-o) / n); n = 1 gives x = o exactly)
+ *        denom = sum_{i=1..n} sum_{k=0..i-1} binoms[i-1, k] (-1)^k / sqrt(k+1) x^(k+1)      (fp32, in this order)
+ *        new_opacities[m] = x;  new_scales[m,:] = (o / denom) scales[m,:]
+ *      opacities [M], scales [M,3] (activated), ratios i32 [M] (read only: clamped in registers), binoms [n_max, n_max]
+ *      (binoms[n,k] = C(n,k)), 1 <= n_max <= 64.
+ *  gspl_mcmc_perturb_means: means [N,3] IN PLACE, means += c(o) Sigma eps, with
+ *        Sigma = R(q) diag(s^2) R(q)^T,  c(o) = coeff / (1 + exp(-100 ((1 - o) - 0.995))),  coeff = noise_lr * means' lr
+ *      raw != 0: scales / rotations / opacities are the model's raw parameters (exp, q / max(|q|, 1e-12), sigmoid inside);
+ *      raw == 0: activated values, rotations used as given.  opacities [N] (or [N,1]).  eps [N,3] from `noise` when not NULL,
+ *      else eps = gspl_mcmc_randn's normals for (seed, offset), generated in registers.
+ *  gspl_mcmc_randn: the generator of the noise, exported for the tests.  Gaussian i draws ONE Philox4x32-10 block with
+ *        key = (lo32(seed), hi32(seed)), counter = (lo32(offset / 4), hi32(offset / 4), lo32(i), hi32(i))
+ *      — curand_init(seed, subsequence = i, offset)'s first block, the layout torch's kernels use with the same generator; the
+ *      caller reserves generator offsets [offset, offset + 4), offset a multiple of 4 (else GSPL_ERR_INVALID_ARG) — giving u32 words b0..b3; u_j = ((b_j >> 8) + 1) 2^-24 in (0, 1]; Box-Muller:
+ *        eps0 = r01 cos(2 pi u1), eps1 = r01 sin(2 pi u1), eps2 = r23 cos(2 pi u3),   r01 = sqrt(-2 log u0), r23 = sqrt(-2 log u2)
+ *      bits u32 [N,4] (nullable), normals [N,3].
+ *  gspl_mcmc_reg_fwd: out[0] = opacity_w mean_i |f(o_i)|, out[1] = scale_w mean_ij |g(s_ij)| (f = sigmoid, g = exp when raw; the
+ *      identity otherwise).  Deterministic: a fixed grid of gspl_mcmc_reg_partials(N) workgroups writes 2 partial sums each to
+ *      `partials`, one workgroup adds them in a fixed order (no atomics).  opacities [N], scales [N,3].
+ *  gspl_mcmc_reg_bwd: v_opacities [N] = grad_out[0] opacity_w / N f'(o) sign(f(o)), v_scales [N,3] = grad_out[1] scale_w / (3N)
+ *      g'(s) sign(g(s)); grad_out [2] f32 on the device (the upstream gradients of out[0], out[1]).
+ * ---------------------------------------------------------------------------------------- */
+int gspl_mcmc_relocation(int M, int n_max, const float* opacities, const float* scales, const int32_t* ratios, const float* binoms,
+                         float* new_opacities, float* new_scales, void* stream);
+int gspl_mcmc_perturb_means(int N, int raw, float* means, const float* scales, const float* rotations, const float* opacities,
+                            const float* noise /*nullable*/, float coeff, uint64_t seed, uint64_t offset, void* stream);
+int gspl_mcmc_randn(int N, uint64_t seed, uint64_t offset, uint32_t* bits /*nullable*/, float* normals, void* stream);
+int gspl_mcmc_reg_partials(int N);         /* workgroups of gspl_mcmc_reg_fwd's first pass: `partials` holds 2x as many floats */
+int gspl_mcmc_reg_fwd(int N, int raw, const float* opacities, const float* scales, float opacity_w, float scale_w,
+                      float* partials, float* out, void* stream);
+int gspl_mcmc_reg_bwd(int N, int raw, const float* opacities, const float* scales, float opacity_w, float scale_w,
+                      const float* grad_out, float* v_opacities, float* v_scales, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
