@@ -168,9 +168,12 @@ struct SplatCull {
 __device__ __forceinline__ SplatCull make_cull(float mx, float my, float a, float b, float c, float opacity) {
     SplatCull s;
     s.mx = mx; s.my = my; s.a = a; s.b = b;
-    const float tau = __logf(255.f * opacity);
     s.det = conic_det(a, b, c);      // (without the cancellation of a c - b b: the spans of long anisotropic splats hang on it)
-    if (!(tau > 0.f)) { s.kind = 0; return s; }
+    // o * vis <= o (vis <= 1): below 1/255 the compositing kernels' `o * vis >= kAlphaMin` never holds.  At or above it, where vis
+    // rounds to 1 the splat contributes, yet 255 * fp32(1/255) rounds to 1 and the log of a product within a few ulps of 1 may be
+    // 0 or negative: tau is clamped to 0 there and the margins below leave a small ellipse round the mean.
+    if (!(opacity >= kAlphaMin)) { s.kind = 0; return s; }
+    const float tau = fmaxf(__logf(255.f * opacity), 0.f);
     if (!(s.det > 0.f) || !(a > 0.f) || !(c > 0.f)) { s.kind = 2; return s; }
     s.kind = 1;
     const float two_tau = 2.f * (tau * 1.001f + 1e-3f);

@@ -340,7 +340,10 @@ __global__ __launch_bounds__(B2_NT, GSPL_BWD2_WAVES) void composite_bwd2_kernel(
                     v2f rw2 = rv2;     // o * vis where the pixel takes a gradient through alpha, else 0
                     if (TR::kClampKillsGrad) rw2 = (v2f){(rv2.x <= TR::kAlphaMax) ? rv2.x : 0.f, (rv2.y <= TR::kAlphaMax) ? rv2.y : 0.f};
                     const v2f om2 = (v2f){1.f, 1.f} - a2;
-                    const v2f ra2 = {__builtin_amdgcn_rcpf(om2.x), __builtin_amdgcn_rcpf(om2.y)};
+                    v2f ra2 = {__builtin_amdgcn_rcpf(om2.x), __builtin_amdgcn_rcpf(om2.y)};
+                    // one Newton step on the 1-ulp hardware reciprocal: T is rebuilt over the whole walk, and an unsaturated walk (after an
+                    // opacity reset) compounds the rcp's error over every entry it takes
+                    ra2 = __builtin_elementwise_fma(ra2, __builtin_elementwise_fma(-om2, ra2, (v2f){1.f, 1.f}), ra2);
                     T2 *= ra2;                                 // transmittance in front of this splat
                     const v2f fac2 = a2 * T2;
                     v2f cdot2 = (v2f){col[0], col[0]} * vo[0];
@@ -491,7 +494,9 @@ __global__ __launch_bounds__(64) void composite_bwd_block_kernel(
             const float a = fminf(TR::kAlphaMax, rv);
             float rw = rv;
             if (TR::kClampKillsGrad) rw = (rv <= TR::kAlphaMax) ? rv : 0.f;
-            const float ra = __builtin_amdgcn_rcpf(1.f - a);
+            const float om = 1.f - a;
+            float ra = __builtin_amdgcn_rcpf(om);
+            ra = fmaf(ra, fmaf(-om, ra, 1.f), ra);      // one Newton step (see the packed walk)
             T *= ra;
             const float fac = a * T;
             float cdot = s_col[k * D] * vo[0];

@@ -52,6 +52,19 @@ def hip_composite_bwd(mode, means2d, conics, colors, opac, bg, W, H, offsets, fl
     return dict(v_means2d=v_xy, v_means2d_abs=v_abs, v_conics=v_con, v_colors=v_col, v_opacities=v_op, hit=hit)
 
 
+# The density controllers' opacity reset (vanilla_density_controller.py, `_reset_opacities`; opacity_reset_value = 0.01): the stored
+# logit becomes inverse_sigmoid(min(sigmoid(logit), value)), so every clamped splat renders at fp32 sigmoid(logit(0.01)) = 0.0099999988.
+RESET_OPACITY = 0.009999998845160007
+
+
+def reset_opacities(opac, value=0.01):
+    """What the model's activated opacities are right after an opacity reset, in fp32 as the reference computes them: the inverse
+    sigmoid log(x / (1 - x)) of min(o, value), then the model's sigmoid."""
+    o = torch.as_tensor(opac, dtype=torch.float32)
+    x = torch.minimum(o, torch.full_like(o, value))
+    return torch.sigmoid(torch.log(x / (1 - x)))
+
+
 EPS32 = 2.0 ** -24
 
 
