@@ -16,7 +16,7 @@ import torch
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSPL_HIP_LIB", os.path.join(_PKG_DIR, "libgspl_hip.so"))   # override: A/B builds of the same ABI
-ABI_VERSION = 38
+ABI_VERSION = 39
 
 GSPL_RECORD_FLOATS = 12
 GSPL_CAMERA_PINHOLE, GSPL_CAMERA_ORTHO, GSPL_CAMERA_FISHEYE = 0, 1, 2
@@ -178,6 +178,14 @@ _SIGNATURES = {
     "gspl_mcmc_reg_partials": (c_int, [c_int]),
     "gspl_mcmc_reg_fwd": (c_int, [c_int, c_int, _P, _P, c_float, c_float, _P, _P, _P]),
     "gspl_mcmc_reg_bwd": (c_int, [c_int, c_int, _P, _P, c_float, c_float, _P, _P, _P, _P]),
+    # section 14 (ABI 39): bilateral-grid slicing and its TV loss (csrc/bilagrid.hip)
+    "gspl_bilagrid_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "gspl_bilagrid_slice_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, c_int, _P, c_int, _P, _P]),
+    "gspl_bilagrid_slice_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, c_int, _P, c_int, _P, c_int,
+                                        _P, _P, c_int, _P, c_size_t, _P]),
+    "gspl_bilagrid_tv_partials": (c_int, [c_int64]),
+    "gspl_bilagrid_tv_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "gspl_bilagrid_tv_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
 }
 
 _LIB = None

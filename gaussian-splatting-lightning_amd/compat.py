@@ -1,6 +1,7 @@
 """Import shims for the reference's un-vendored native packages that this package replaces.
 
-Besides the two small helpers below (`simple_knn`, `fused_ssim`), `install()` registers stand-ins for the rasterizer
+Besides the small helpers below (`simple_knn`, `fused_ssim`, and `fused_bilagrid` — the bilateral-grid processor's slice and TV
+loss, bound late to `gspl_amd.bilagrid`), `install()` registers stand-ins for the rasterizer
 packages themselves — `diff_gaussian_rasterization`, Taming 3DGS's `diff_accel_gaussian_rasterization`, 2DGS's
 `diff_surfel_rasterization` and the yzslab `gsplat` fork — under the module paths and function names the
 reference imports (internal/renderers/vanilla_renderer.py:4, gsplat_renderer.py:2-4, gsplat_v1_renderer.py:8-20,
@@ -34,13 +35,12 @@ def _missing(name: str) -> bool:
         return True
 
 
-def _late(name: str):
-    """Call-time binding to `gspl_amd.ops.<name>` (so that the op can be looked up — or replaced in a test — after install)."""
+def _late(name: str, module: str = "ops"):
+    """Call-time binding to `gspl_amd.<module>.<name>` (so that it can be looked up — or replaced in a test — after install)."""
     def fn(*args, **kwargs):
-        from . import ops
-        return getattr(ops, name)(*args, **kwargs)
+        return getattr(importlib.import_module(f"{__package__}.{module}"), name)(*args, **kwargs)
     fn.__name__ = fn.__qualname__ = name
-    fn.__doc__ = f"gspl_amd.ops.{name} (HIP)"
+    fn.__doc__ = f"gspl_amd.{module}.{name} (HIP)"
     return fn
 
 
@@ -154,4 +154,8 @@ def install() -> list:
         mod.fused_ssim = ops.fused_ssim
         sys.modules["fused_ssim"] = mod
         installed.append("fused_ssim")
+    if _missing("fused_bilagrid"):
+        _module("fused_bilagrid", "gspl_amd stand-in for fused_bilagrid (HIP; gspl_amd.bilagrid)",
+                **{n: _late(n, "bilagrid") for n in ("BilateralGrid", "slice", "total_variation_loss")})
+        installed.append("fused_bilagrid")
     return installed

@@ -6,10 +6,43 @@ i.e. before its CLI has parsed `--model.renderer`: the stand-ins of `gspl_amd.co
 entry point is imported.  This launcher does exactly that and then runs the script unchanged, as `python <script> [args...]` would:
 
     python -m gspl_amd.launch main.py fit --data.path data/lego --model.renderer gspl_amd.renderers.HipVanillaRenderer
+
+It also lets `torch.optim.lr_scheduler.LambdaLR` take the `verbose=` keyword that newer torch releases removed: the reference passes
+`verbose=False` (internal/output_processors/bilagrid.py and exposure.py, the appearance-embedding, deformable, SWAG and RGB-MLP
+renderers).  Only in this launched process, and only when the installed torch rejects the keyword; importing the package patches
+nothing in torch.
 """
+import inspect
 import os
 import runpy
 import sys
+
+
+def _lambdalr_takes_verbose(cls) -> bool:
+    try:
+        params = inspect.signature(cls.__init__).parameters.values()
+    except (TypeError, ValueError):
+        return True
+    return any(p.name == "verbose" or p.kind is p.VAR_KEYWORD for p in params)
+
+
+def accept_lambdalr_verbose() -> bool:
+    """Replace `torch.optim.lr_scheduler.LambdaLR` by a subclass that accepts and ignores `verbose` when the installed torch rejects
+    it; returns whether it did."""
+    from torch.optim import lr_scheduler
+    base = lr_scheduler.LambdaLR
+    if _lambdalr_takes_verbose(base):
+        return False
+
+    class LambdaLR(base):
+        __doc__ = base.__doc__
+
+        def __init__(self, optimizer, lr_lambda, last_epoch=-1, verbose=None):
+            super().__init__(optimizer, lr_lambda, last_epoch)
+
+    LambdaLR.__module__, LambdaLR.__qualname__ = base.__module__, base.__qualname__
+    lr_scheduler.LambdaLR = LambdaLR
+    return True
 
 
 def main(argv=None):
@@ -18,6 +51,7 @@ def main(argv=None):
         sys.exit("usage: python -m gspl_amd.launch <script.py> [args...]")
     from . import compat
     compat.install()
+    accept_lambdalr_verbose()
     script = argv[0]
     sys.argv = argv
     sys.path.insert(0, os.path.dirname(os.path.abspath(script)))      # what `python <script>` puts first

@@ -13,6 +13,8 @@ reference's renderers call (same names, argument meaning and error behaviour):
       SurfelRasterizationSettings, SurfelGaussianRasterizer
   3DGS-MCMC (internal/density_controllers/mcmc_density_controller.py:13, `gsplat.relocation`; not registered in compat)
       compute_relocation, perturb_means_, mcmc_regularization
+  Bilateral grid (internal/output_processors/bilagrid.py, `fused_bilagrid`; the module-level API is gspl_amd.bilagrid)
+      bilagrid_slice, bilagrid_tv
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -40,6 +42,7 @@ from .inria import (GaussianRasterizationSettings, GaussianRasterizer, _InriaRas
                     AccelRasterizationSettings, AccelGaussianRasterizer)
 from .surfel import SurfelRasterizationSettings, SurfelGaussianRasterizer, rasterize_surfels, _SurfelRasterizeFn
 from .mcmc import compute_relocation, perturb_means_, mcmc_regularization, mcmc_randn, _MCMCRegFn
+from .bilagrid import bilagrid_slice, bilagrid_tv, _SliceFn, _TvFn
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

@@ -786,6 +786,44 @@ int gspl_mcmc_reg_fwd(int N, int raw, const float* opacities, const float* scale
 int gspl_mcmc_reg_bwd(int N, int raw, const float* opacities, const float* scales, float opacity_w, float scale_w,
                       const float* grad_out, float* v_opacities, float* v_scales, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 14. Bilateral-grid slicing and its total-variation loss (ABI 39; csrc/bilagrid.hip): what `fused_bilagrid`'s `slice` and
+ *    `total_variation_loss` compute for the reference's output processor (internal/output_processors/bilagrid.py), with the
+ *    semantics of internal/utils/lib_bilagrid.py (`F.grid_sample(align_corners=True, padding_mode='border')`, then the affine).
+ *
+ *  grids [N, 12, L, GH, GW] (the 12 channels a row-major 3x4 matrix); bounds: 1 <= N <= 65535, L <= 28, GH, GW <= 1024,
+ *  L GH GW <= 16384 (else GSPL_ERR_INVALID_ARG).  Images: B of H x W pixels; xy [B, H, W, 2] (xy_bstride = H W 2) or one [H, W, 2]
+ *  for all (xy_bstride = 0); rgb, out, grad_out, grad_rgb hold 3 H W floats per image (image stride 3 H W), each in `layout`
+ *  GSPL_LAYOUT_HWC (interleaved) or GSPL_LAYOUT_CHW (planar).  Image b uses grid idx[b * idx_stride] (i32, read on the device;
+ *  idx_stride = 0: one index for all).  An index outside [0, N) reads nothing: that image's out and grad_rgb are NaN and its
+ *  pixels add nothing to grad_grids.
+ *  gspl_bilagrid_slice_fwd, per pixel with colour c and (x, y):
+ *        z = 2 (0.299 c0 + 0.587 c1 + 0.114 c2) - 1 (not clamped);  u = ((2x - 1 + 1) / 2)(GW - 1), v likewise with y, GH,
+ *        w = ((z + 1) / 2)(L - 1), each clamped to [0, size - 1] (evaluated in fp64 as x (GW - 1), y (GH - 1), gray (L - 1));
+ *        A_k = trilinear sample of grids[idx_b][k] at (w, v, u);
+ *        out_i = sum_{j<3} A_{4i+j} c_j + A_{4i+3}.
+ *  gspl_bilagrid_slice_bwd: grad_rgb (nullable) dc_j = sum_i dout_i A_{4i+j} + (L - 1) wgt_j sum_k dA_k (B_k(z0+1) - B_k(z0)) with
+ *      dA_{4i+j} = dout_i c_j, dA_{4i+3} = dout_i, B_k the bilinear sample at level z; the w term is 0 where w was clamped or lies
+ *      on 0 or L - 1.  grad_grids (nullable) [N, 12, L, GH, GW], dense, every element written: the trilinear scatter of dA, zero for
+ *      grids no image selects.  Deterministic, no float atomics: one workgroup per pixel block sums its pixels in a fixed order into
+ *      a slab row (`workspace`, gspl_bilagrid_workspace_bytes(L, GH, GW, B, H, W) bytes, 16-byte aligned); a second kernel adds
+ *      the rows covering each element in block order.  The workspace's contents on entry do not matter.
+ *  gspl_bilagrid_tv_fwd: out[0] = (1/N) sum_d S_d / K_d over x [N, C, L, GH, GW], S_d the sum of squared neighbour differences
+ *      along d, K_d = C (n_d - 1) prod_{e != d} n_e (a term with n_d = 1 is 0).  Two-level fixed-order sum over
+ *      gspl_bilagrid_tv_partials(N C L GH GW) partials (f32 scratch).  gspl_bilagrid_tv_bwd: grad_x = grad_out[0] dTV/dx
+ *      (grad_out on the device).
+ * ---------------------------------------------------------------------------------------- */
+size_t gspl_bilagrid_workspace_bytes(int L, int GH, int GW, int B, int H, int W);
+int gspl_bilagrid_slice_fwd(int N, int L, int GH, int GW, int B, int H, int W, const float* grids, const float* xy, int64_t xy_bstride,
+                            const float* rgb, int layout, const int32_t* idx, int idx_stride, float* out, void* stream);
+int gspl_bilagrid_slice_bwd(int N, int L, int GH, int GW, int B, int H, int W, const float* grids, const float* xy, int64_t xy_bstride,
+                            const float* rgb, int layout, const int32_t* idx, int idx_stride, const float* grad_out, int go_layout,
+                            float* grad_grids /*nullable*/, float* grad_rgb /*nullable*/, int gr_layout, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int gspl_bilagrid_tv_partials(int64_t n);
+int gspl_bilagrid_tv_fwd(int N, int C, int L, int GH, int GW, const float* x, float* partials, float* out, void* stream);
+int gspl_bilagrid_tv_bwd(int N, int C, int L, int GH, int GW, const float* x, const float* grad_out, float* grad_x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
