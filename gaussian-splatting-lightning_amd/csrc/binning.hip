@@ -103,8 +103,6 @@ __global__ void fill_i32_kernel(int n, int32_t v, int32_t* __restrict__ p) {
     if (i < n) p[i] = v;
 }
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 static inline int key_bits(int n_tiles) {
     int b = 0;
     while ((1ll << b) < (long long)n_tiles) ++b;
@@ -124,13 +122,12 @@ struct IsectWorkspace {
 static int plan_workspace(int N, int64_t n_isects, int key_bits_total, IsectWorkspace& w) {
     const size_t n = (size_t)(N > 0 ? N : 1), ni = (size_t)(n_isects > 0 ? n_isects : 1);
     if (ni > RADIX_MAX_ITEMS || n > RADIX_MAX_ITEMS) { set_error("isect", "more than 2^30-1 items"); return GSPL_ERR_UNSUPPORTED; }
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    w.counts_off = take(4 * n);
-    w.scan_off = take(scan_workspace_bytes(n));
-    w.total_count = off;
-    w.keys_off = take(8 * ni);
-    w.vals_off = take(4 * ni);
+    Carve c;
+    w.counts_off = c.take(4 * n);
+    w.scan_off = c.take(scan_workspace_bytes(n));
+    w.total_count = c.off;
+    w.keys_off = c.take(8 * ni);
+    w.vals_off = c.take(4 * ni);
     const int split = key_bits_total > 32 ? 24 : 0;
     w.two_sorts = key_bits_total > 32;
     bool ok = true;
@@ -138,8 +135,8 @@ static int plan_workspace(int N, int64_t n_isects, int key_bits_total, IsectWork
     else ok = radix_plan(ni, 0, key_bits_total, 8, RADIX_TILE_U64, w.lo);
     if (!ok) { set_error("isect", "key bits not representable"); return GSPL_ERR_UNSUPPORTED; }
     w.sort_bytes = w.lo.total_bytes > (w.two_sorts ? w.hi.total_bytes : 0) ? w.lo.total_bytes : w.hi.total_bytes;
-    w.sort_off = take(w.sort_bytes);
-    w.total = off;
+    w.sort_off = c.take(w.sort_bytes);
+    w.total = c.off;
     return GSPL_OK;
 }
 
@@ -510,23 +507,22 @@ struct BinWorkspace {
 static int plan_bin(int N, int64_t n_isects, int n_tiles, BinWorkspace& w) {
     const size_t n = (size_t)(N > 0 ? N : 1), ni = (size_t)(n_isects > 0 ? n_isects : 1);
     if (n > RADIX_MAX_ITEMS || ni > RADIX_MAX_ITEMS) { set_error("bin", "more than 2^30-1 splats or intersections"); return GSPL_ERR_UNSUPPORTED; }
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    w.keys_off = take(4 * n); w.ids_off = take(4 * n); w.keys2_off = take(4 * n);
-    w.counts_off = take(4 * n);
+    Carve c;
+    w.keys_off = c.take(4 * n); w.ids_off = c.take(4 * n); w.keys2_off = c.take(4 * n);
+    w.counts_off = c.take(4 * n);
     if (!radix_plan(n, 0, 32, 8, RADIX_TILE_U32, w.depth)) return fail_arg("bin: depth sort plan");
     w.scan_states_off = w.depth.total_bytes;          // the scan's block sums follow the sort's tables
     w.sort1_bytes = w.depth.total_bytes + scan_workspace_bytes(n);
-    w.sort1_off = take(w.sort1_bytes);
-    w.total_count = off;
-    w.tkeys_off = take(8 * ni); w.tkeys2_off = take(8 * ni);
+    w.sort1_off = c.take(w.sort1_bytes);
+    w.total_count = c.off;
+    w.tkeys_off = c.take(8 * ni); w.tkeys2_off = c.take(8 * ni);
     // n_tiles <= 0: size query (the tile grid is not known to gspl_bin_workspace_bytes) -> the widest plan, four passes
     int bits = n_tiles > 0 ? key_bits(n_tiles) - 32 : 32;
     if (bits < 2) bits = 2;                             // at least two passes: the pass before the last clears the tile counters
     if (!radix_plan(ni, 32, 32 + bits, bits > 8 ? 8 : (bits + 1) / 2, RADIX_TILE_U64, w.tile) || w.tile.passes < 2) return fail_arg("bin: tile sort plan");
     w.sort2_bytes = w.tile.total_bytes;
-    w.sort2_off = take(w.sort2_bytes);
-    w.total = off;
+    w.sort2_off = c.take(w.sort2_bytes);
+    w.total = c.off;
     return GSPL_OK;
 }
 

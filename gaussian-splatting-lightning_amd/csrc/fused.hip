@@ -20,8 +20,6 @@
 
 namespace gspl {
 
-static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // per-splat intermediates of one frame, carved out of ONE allocation (tag GSPL_BUF_GEOMETRY)
 struct GeomLayout {
     size_t radii, means2d, depths, conics, colors, clamped, cov3d, sh_jac, order, cum, big_list, spans, opac, colors4, total;
@@ -29,36 +27,23 @@ struct GeomLayout {
 // invdepth (GSPL_INRIA_INVDEPTH): one more region, the [N,4] rows compositing reads (colour | 1 / z)
 static GeomLayout geom_layout(size_t n, bool invdepth = false) {
     GeomLayout g;
-    size_t off = 0;
-    auto take = [&](size_t b) { size_t o = off; off = up256(off + b); return o; };
-    g.means2d = take(8 * n); g.depths = take(4 * n); g.conics = take(12 * n); g.colors = take(12 * n);
-    g.clamped = take(3 * n); g.cov3d = take(24 * n); g.sh_jac = take(36 * n);
-    g.order = take(4 * n); g.cum = take(8 * (n + 1)); g.big_list = take(4 * n); g.spans = take((size_t)GSPL_BIN_SPAN_BYTES * n);
-    g.opac = take(4 * n);
-    g.colors4 = invdepth ? take(16 * n) : 0;
+    Carve c;
+    g.means2d = c.take(8 * n); g.depths = c.take(4 * n); g.conics = c.take(12 * n); g.colors = c.take(12 * n);
+    g.clamped = c.take(3 * n); g.cov3d = c.take(24 * n); g.sh_jac = c.take(36 * n);
+    g.order = c.take(4 * n); g.cum = c.take(8 * (n + 1)); g.big_list = c.take(4 * n); g.spans = c.take((size_t)GSPL_BIN_SPAN_BYTES * n);
+    g.opac = c.take(4 * n);
+    g.colors4 = invdepth ? c.take(16 * n) : 0;
     g.radii = 0;       // radii are an OUTPUT tensor of the call, not part of the block
-    g.total = off;
+    g.total = c.off;
     return g;
 }
 struct ImageLayout { size_t alphas, final_Ts, last_ids, offsets, total; };
 static ImageLayout image_layout(size_t pixels, size_t tiles) {
     ImageLayout m;
-    size_t off = 0;
-    auto take = [&](size_t b) { size_t o = off; off = up256(off + b); return o; };
-    m.alphas = take(4 * pixels); m.final_Ts = take(4 * pixels); m.last_ids = take(4 * pixels); m.offsets = take(4 * (tiles + 1));
-    m.total = off;
+    Carve c;
+    m.alphas = c.take(4 * pixels); m.final_Ts = c.take(4 * pixels); m.last_ids = c.take(4 * pixels); m.offsets = c.take(4 * (tiles + 1));
+    m.total = c.off;
     return m;
-}
-
-// one pinned 32-byte block per host thread for the read-back (cum[N-1] = the list length, cum[N] = n_big)
-static int64_t* pinned_words() {
-    static thread_local int64_t* p = nullptr;
-    if (!p) {
-        void* q = nullptr;
-        if (hipHostMalloc(&q, 4 * sizeof(int64_t), hipHostMallocDefault) != hipSuccess) return nullptr;
-        p = (int64_t*)q;
-    }
-    return p;
 }
 
 // The host's wait for the frame's one number (the list length): it POLLS the pinned word the scan kernel stores its ticket into.
@@ -385,8 +370,9 @@ extern "C" int gspl_rasterize_inria_fwd(
             const unsigned long long ticket = next_ticket();
             rc = bin_count_ticket(N, GSPL_MODE_INRIA, st->means2d, radii, st->depths, st->conics, opacities, tile, tile_w, tile_h, order, cum, big_list,
                                   spans, host, ws1, ws1_bytes, s, ticket, true, zero_tile);      // the scan kernel stores the two numbers, then the ticket, into `host`
-            if (rc != GSPL_OK) return rc;
+            // every return from here on has waited for the scan: `host` is the thread's one block (pinned_words), free again after the call
             auto wait_count = [&]() -> bool { return wait_for_ticket(host, ticket, s); };
+            if (rc != GSPL_OK) { (void)wait_count(); return rc; }
             // speculative emission with the caller's guess of the list length, while the host waits for the real one
             if (ws2) {
                 rc = bin_emit_impl(N, GSPL_MODE_INRIA, st->means2d, radii, st->conics, opacities, order, cum, big_list, spans, tile, tile_w, tile_h,

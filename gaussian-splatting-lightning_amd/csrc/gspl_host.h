@@ -32,6 +32,26 @@ inline int check_hip(hipError_t e, const char* where) {
     return GSPL_OK;
 }
 
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// One block carved into regions in the order they are taken, each starting on a 256-byte boundary; `off` ends as the block's size.
+struct Carve {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off = up256(off + bytes); return o; }
+};
+
+// The pinned host words a binning scan stores the frame's list length into: one block of four per host thread, kept for the process.
+// The calls that use it read their words before they return.  NULL (HIP's error cleared) when it cannot be allocated.
+inline int64_t* pinned_words() {
+    static thread_local int64_t* p = nullptr;
+    if (!p) {
+        void* q = nullptr;
+        if (hipHostMalloc(&q, 4 * sizeof(int64_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        p = (int64_t*)q;
+    }
+    return p;
+}
+
 }  // namespace gspl
 
 // internal launchers shared between translation units (sh.hip -> inria.hip)

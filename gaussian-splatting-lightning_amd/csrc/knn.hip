@@ -195,8 +195,6 @@ struct KnnWorkspace {
 };
 static constexpr size_t KNN_MAX_CELLS = (size_t)KNN_MAX_DIM * KNN_MAX_DIM * KNN_MAX_DIM;
 
-static inline size_t knn_align(size_t x) { return (x + 255) / 256 * 256; }
-
 // cells actually allocated: the grid never has more than ~N / TARGET * 8 cells unless an axis hits the 256 clamp
 static size_t knn_cell_capacity(int N) {
     const size_t want = (size_t)N * 4 + 4096;
@@ -206,18 +204,17 @@ static size_t knn_cell_capacity(int N) {
 static int plan_knn(int N, KnnWorkspace& w) {
     const size_t n = (size_t)(N > 0 ? N : 1), cells = knn_cell_capacity(N);
     const size_t scan_tmp = exclusive_scan_u32_workspace_bytes(cells + 1);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = knn_align(off + bytes); return o; };
-    w.bounds_off = take(8 * 4);
-    w.grid_off = take(sizeof(KnnGrid));
-    w.cell_id_off = take(4 * n);
-    w.count_off = take(4 * (cells + 1));
-    w.start_off = take(4 * (cells + 1));
-    w.cursor_off = take(4 * (cells + 1));
-    w.sorted_off = take(16 * n);
+    Carve c;
+    w.bounds_off = c.take(8 * 4);
+    w.grid_off = c.take(sizeof(KnnGrid));
+    w.cell_id_off = c.take(4 * n);
+    w.count_off = c.take(4 * (cells + 1));
+    w.start_off = c.take(4 * (cells + 1));
+    w.cursor_off = c.take(4 * (cells + 1));
+    w.sorted_off = c.take(16 * n);
     w.scan_tmp_bytes = scan_tmp;
-    w.scan_tmp_off = take(scan_tmp);
-    w.total = off;
+    w.scan_tmp_off = c.take(scan_tmp);
+    w.total = c.off;
     return GSPL_OK;
 }
 

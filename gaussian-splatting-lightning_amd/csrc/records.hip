@@ -16,7 +16,6 @@
 namespace gspl {
 
 static constexpr int REC = 12;
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 __global__ __launch_bounds__(256) void records_flag_kernel(int64_t total, const int32_t* __restrict__ radii, uint32_t* __restrict__ flags) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -167,11 +166,10 @@ __global__ __launch_bounds__(256) void records_unpack_bwd_kernel(
 
 struct RecordsWorkspace { size_t flags_off, scan_off, tmp_off, total; };
 static void plan_records(int64_t total, RecordsWorkspace& w) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    Carve c;
     const size_t n = (size_t)(total > 0 ? total : 1);
-    w.flags_off = take(4 * n); w.scan_off = take(4 * n); w.tmp_off = take(exclusive_scan_u32_workspace_bytes(n));
-    w.total = off;
+    w.flags_off = c.take(4 * n); w.scan_off = c.take(4 * n); w.tmp_off = c.take(exclusive_scan_u32_workspace_bytes(n));
+    w.total = c.off;
 }
 
 }  // namespace gspl

@@ -482,38 +482,23 @@ __global__ __launch_bounds__(256) void surfel_preprocess_bwd_kernel(
     }
 }
 
-static inline size_t up256s(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct SurfelGeomLayout { size_t means2d, depths, rec, colors, clamped, order, cum, big_list, spans, total; };
 static SurfelGeomLayout surfel_geom_layout(size_t n) {
     SurfelGeomLayout g;
-    size_t off = 0;
-    auto take = [&](size_t b) { size_t o = off; off = up256s(off + b); return o; };
-    g.rec = take(4 * SURF_REC * n); g.means2d = take(8 * n); g.depths = take(4 * n); g.colors = take(12 * n); g.clamped = take(3 * n);
-    g.order = take(4 * n); g.cum = take(8 * (n + 1)); g.big_list = take(4 * n); g.spans = take((size_t)GSPL_BIN_SPAN_BYTES * n);
-    g.total = off;
+    Carve c;
+    g.rec = c.take(4 * SURF_REC * n); g.means2d = c.take(8 * n); g.depths = c.take(4 * n); g.colors = c.take(12 * n); g.clamped = c.take(3 * n);
+    g.order = c.take(4 * n); g.cum = c.take(8 * (n + 1)); g.big_list = c.take(4 * n); g.spans = c.take((size_t)GSPL_BIN_SPAN_BYTES * n);
+    g.total = c.off;
     return g;
 }
 struct SurfelImageLayout { size_t final_T, M1, M2, last, median, offsets, total; };
 static SurfelImageLayout surfel_image_layout(size_t pixels, size_t tiles) {
     SurfelImageLayout m;
-    size_t off = 0;
-    auto take = [&](size_t b) { size_t o = off; off = up256s(off + b); return o; };
-    m.final_T = take(4 * pixels); m.M1 = take(4 * pixels); m.M2 = take(4 * pixels); m.last = take(4 * pixels); m.median = take(4 * pixels);
-    m.offsets = take(4 * (tiles + 1));
-    m.total = off;
+    Carve c;
+    m.final_T = c.take(4 * pixels); m.M1 = c.take(4 * pixels); m.M2 = c.take(4 * pixels); m.last = c.take(4 * pixels); m.median = c.take(4 * pixels);
+    m.offsets = c.take(4 * (tiles + 1));
+    m.total = c.off;
     return m;
-}
-
-// the pinned host words the binning's scan stores the list length into (one block per host thread, kept for the process)
-static int64_t* surfel_pinned_words() {
-    static thread_local int64_t* p = nullptr;
-    if (!p) {
-        void* q = nullptr;
-        if (hipHostMalloc(&q, 4 * sizeof(int64_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        p = (int64_t*)q;
-    }
-    return p;
 }
 
 }  // namespace gspl
@@ -561,7 +546,7 @@ extern "C" int gspl_rasterize_surfel_fwd(
         }
         const size_t ws1_bytes = gspl_bin_workspace_bytes(N, 0);
         void* ws1 = alloc(alloc_ctx, GSPL_BUF_BINNING, ws1_bytes);
-        int64_t* host = surfel_pinned_words();
+        int64_t* host = pinned_words();
         if (!ws1) return fail_arg("rasterize_surfel_fwd: allocation call-back returned NULL");
         if (!host) return fail_arg("rasterize_surfel_fwd: no pinned host word");
         int32_t* order = (int32_t*)(geom + g.order);
@@ -571,10 +556,11 @@ extern "C" int gspl_rasterize_surfel_fwd(
         host[0] = -1;
         rc = gspl_bin_count(N, GSPL_MODE_INRIA, st->means2d, radii, st->depths, nullptr, nullptr, 16, tile_w, tile_h, order, cum, big_list, spans,
                             host, ws1, ws1_bytes, stream);
+        // the frame's one read-back: the list length, stored into pinned memory by the scan (also waited for when the count failed: the
+        // scan may be in flight, and `host` is the thread's one block)
+        const int rc_sync = check_hip(hipStreamSynchronize(s), "rasterize_surfel_fwd: list length");
         if (rc != GSPL_OK) return rc;
-        // the frame's one read-back: the list length, stored into pinned memory by the scan
-        rc = check_hip(hipStreamSynchronize(s), "rasterize_surfel_fwd: list length");
-        if (rc != GSPL_OK) return rc;
+        if (rc_sync != GSPL_OK) return rc_sync;
         n_isects = host[0];
         if (n_isects < 0) return fail_arg("rasterize_surfel_fwd: the list length never arrived");
         if (n_isects > (int64_t)((1u << 30) - 1u)) {
@@ -631,8 +617,8 @@ extern "C" int gspl_rasterize_surfel_bwd(
             if (!alloc) return fail_arg("rasterize_surfel_bwd: the deterministic mode needs the allocation call-back");
             while (id_bits < 32 && (1ll << id_bits) < (long long)N) ++id_bits;
             sort_ws_bytes = gspl_radix_sort_workspace_bytes(n_isects, 4, 0, id_bits);
-            const size_t ent_bytes = up256s((size_t)n_isects * SURF_GRAD * sizeof(float));
-            const size_t key_bytes = up256s((size_t)n_isects * 4 * sizeof(uint32_t));
+            const size_t ent_bytes = up256((size_t)n_isects * SURF_GRAD * sizeof(float));
+            const size_t key_bytes = up256((size_t)n_isects * 4 * sizeof(uint32_t));
             char* blk = (char*)alloc(alloc_ctx, GSPL_BUF_SURFEL_ENTRIES, ent_bytes + key_bytes + (sort_ws_bytes ? sort_ws_bytes : 16));
             if (!blk) return fail_arg("rasterize_surfel_bwd: allocation call-back returned NULL");
             entries = (float*)blk; keys = (uint32_t*)(blk + ent_bytes); sort_ws = blk + ent_bytes + key_bytes;

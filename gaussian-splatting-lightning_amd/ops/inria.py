@@ -9,6 +9,7 @@ from torch import Tensor
 
 from .. import _lib as L
 from ._state import STATE as S
+from ._frame import FrameBlocks
 from ._common import (_SUPPORTED_D, _packed_row_stride, _guarded, _f32c, _rows, _raw_ptr, _grad_or_zeros, _side_stream, colour_stream,
                       join_pending_updates, _await_updates, _take_event)
 from .binning import MAX_ISECTS, bin_gaussians_begin, bin_gaussians_end
@@ -168,32 +169,6 @@ class _InriaRasterizeFn(torch.autograd.Function):
 # colour kernel alone (1.280 / 1.280 vs 1.292 / 1.273 ms per step), and with the deferred shs_rest update on the same stream the
 # default priority is the faster one (1.251 / 1.257 vs 1.266 / 1.264) — and the only two runs with 6-9 ms stalls of single steps had
 # the low-priority stream carrying the update.  Default: the default priority.
-_ALLOC_TLS = __import__("threading").local()
-
-
-def _alloc_trampoline(_ctx, tag, nbytes):
-    """`gspl_alloc_fn`: hand the library a block of torch-owned device memory; the tensors stay with the caller's holder."""
-    holder = _ALLOC_TLS.holder
-    try:
-        t = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=holder["device"])
-        holder.setdefault(tag, []).append(t)
-        return t.data_ptr()
-    except Exception as e:      # an exception must not cross the C boundary: NULL = failure, re-raised by the caller
-        holder["error"] = e
-        return 0
-
-
-_ALLOC_CB = L.ALLOC_FN(_alloc_trampoline)
-
-
-def _view(buf: Tensor, ptr: int, shape, dtype) -> Tensor:
-    """Typed view of a region of a byte buffer the library carved up (ptr = device address inside `buf`)."""
-    import math
-    off = ptr - buf.data_ptr()
-    nbytes = math.prod(shape) * torch.empty((), dtype=dtype).element_size()
-    return buf[off:off + nbytes].view(dtype).view(shape)
-
-
 class _InriaFusedFn(torch.autograd.Function):
     @staticmethod
     @_guarded(1)
@@ -228,8 +203,6 @@ class _InriaFusedFn(torch.autograd.Function):
         state.flags |= (L.GSPL_INRIA_ANTIALIAS if antialias else 0) | (L.GSPL_INRIA_INVDEPTH if invdepth else 0)
         if will_backward:
             state.flags |= L.GSPL_INRIA_WILL_BACKWARD      # the forward's compositing kernel clears the backward's packed rows (no fill command there)
-        holder = {"device": dev}
-        _ALLOC_TLS.holder = holder
         side = _side_stream(dev)
         with torch.cuda.device(dev):
             side_handle = None
@@ -246,22 +219,15 @@ class _InriaFusedFn(torch.autograd.Function):
             # geometry parameters are read on the CALLER's stream (also in place with raw_params): an update of theirs in flight on
             # the colour stream has to be over first (FusedAdam(deferred=("scales", ...)): "kernels of this package wait by themselves")
             _await_updates(means3D, scales, rotations, opac)
-            try:
+            with FrameBlocks(dev) as frame:
                 L.call("gspl_rasterize_inria_fwd", N, int(s.sh_degree), n_coeffs, L.ptr(means3D), L.ptr(scales), L.ptr(rotations),
                        L.ptr(cov3D_precomp), L.ptr(sh), L.ptr(sh_rest), L.ptr(colors_precomp), L.ptr(opac), L.ptr(viewm), L.ptr(projm), L.ptr(campos), L.ptr(bg),
-                       W, H, float(s.tanfovx), float(s.tanfovy), float(s.scale_modifier), _ALLOC_CB, None, hint,
+                       W, H, float(s.tanfovx), float(s.tanfovy), float(s.scale_modifier), frame.callback, None, hint,
                        L.ptr(out), L.ptr(radii), ctypes.byref(state), L.stream(), side_handle)
-            except RuntimeError:
-                if "error" in holder:
-                    raise holder["error"]
-                raise
-            finally:
-                _ALLOC_TLS.holder = None
         if side.enabled and not low:
             # blocks the colour kernel used on the side stream are freed by the caller's stream: tell the allocator
             # (the library's own low-priority stream is joined inside the call: stream order on the caller's stream covers it)
-            for t in holder.get(L.GSPL_BUF_GEOMETRY, []):
-                t.record_stream(side.stream)
+            frame.kept[L.GSPL_BUF_GEOMETRY].record_stream(side.stream)
         S.last_isects[key] = int(state.n_isects)
         S.capacity.observe(key, N, int(state.n_isects))
         S.speculation["frames"] += 1
@@ -269,48 +235,37 @@ class _InriaFusedFn(torch.autograd.Function):
             S.speculation["cold"] += 1
         elif int(state.n_isects) > hint:
             S.speculation["misses"] += 1
-        holder.pop(L.GSPL_BUF_BINNING, None)           # scratch of the count half and of the tile sort: not needed again
-        holder.pop(L.GSPL_BUF_LISTS_WORK, None)
-        # The frame's device buffers (projected splats, tile lists, per-pixel state, checkpoints: torch byte tensors the library carved up)
-        # are SAVED TENSORS of the node: autograd frees them when the graph is released — right after the backward, or, with
-        # `retain_graph=True`, when the graph dies — and a second backward through a released graph raises autograd's own error, as with
-        # the Inria op this replaces (round 6, VERDICT r5 #8b: rounds 1-5 dropped the buffers by hand after the first backward).
-        for tag in (L.GSPL_BUF_LISTS, L.GSPL_BUF_CHECKPOINTS):      # a frame whose room was too small allocated these twice: the first blocks are abandoned
-            if len(holder.get(tag, ())) > 1:
-                holder[tag] = holder[tag][-1:]
-        frame_buffers = [t for tag, ts in holder.items() if isinstance(ts, list) for t in ts]
-        ctx.save_for_backward(means3D, scales, rotations, sh, opac, viewm, projm, campos, bg, radii, sh_rest, *frame_buffers)
-        ctx.state, ctx.backwards_run = state, 0
-        ctx.packed_at = holder[L.GSPL_BUF_PACKED][-1].data_ptr() if (state.flags & L.GSPL_INRIA_PACKED_READY) else 0
-        # (the error slot must not outlive the call: an allocation the library handled gracefully — checkpoints it can do without — is not an error)
-        holder.pop("error", None)
         ctx.cfg = (H, W, int(s.sh_degree), n_coeffs, float(s.tanfovx), float(s.tanfovy), float(s.scale_modifier), colors_precomp is not None,
                    cov3D_precomp is not None, opacities.shape, D)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(radii)
         ctx.means2D_ref = means2D
         if S.keep_last_raster:
-            geom, lists = holder[L.GSPL_BUF_GEOMETRY][0], holder.get(L.GSPL_BUF_LISTS, [None])[-1]
-            img = holder[L.GSPL_BUF_IMAGE][0]
             nI = int(state.n_isects)
-            S.last_raster = dict(mode=L.GSPL_MODE_INRIA, width=W, height=H, means2d=_view(geom, state.means2d, (N, 2), torch.float32),
-                               conics=_view(geom, state.conics, (N, 3), torch.float32),
-                               opacities=(_view(geom, state.opacities, (N,), torch.float32) if (raw_params or antialias) else opac),
-                               colors=_view(geom, state.colors, (N, D), torch.float32),
-                               flatten_ids=(lists[:4 * nI].view(torch.int32) if lists is not None else torch.empty(0, dtype=torch.int32, device=dev)),
-                               offsets=_view(img, state.offsets, (tile_w * tile_h,), torch.int32), radii=radii,
-                               depths=_view(geom, state.depths, (N,), torch.float32),
-                               last_ids=_view(img, state.last_ids, (H, W), torch.int32),
+            S.last_raster = dict(mode=L.GSPL_MODE_INRIA, width=W, height=H, means2d=frame.view(state.means2d, (N, 2), torch.float32),
+                               conics=frame.view(state.conics, (N, 3), torch.float32),
+                               opacities=(frame.view(state.opacities, (N,), torch.float32) if (raw_params or antialias) else opac),
+                               colors=frame.view(state.colors, (N, D), torch.float32),
+                               flatten_ids=(frame.view(state.flatten_ids, (nI,), torch.int32) if state.flatten_ids else torch.empty(0, dtype=torch.int32, device=dev)),
+                               offsets=frame.view(state.offsets, (tile_w * tile_h,), torch.int32), radii=radii,
+                               depths=frame.view(state.depths, (N,), torch.float32),
+                               last_ids=frame.view(state.last_ids, (H, W), torch.int32),
                                # segmented backward: the word in which the backward counts the segments it published (beyond each tile's
                                # first; 0 after a backward: every walk was short; None: no checkpoints were taken)
-                               segment_count=(_view(holder[L.GSPL_BUF_CHECKPOINTS][-1], state.seg_words, (1,), torch.int32) if state.seg_ckpt else None))
+                               segment_count=(frame.view(state.seg_words, (1,), torch.int32) if state.seg_ckpt else None))
+        # The frame's device blocks (projected splats, tile lists, per-pixel state, checkpoints, packed rows) are SAVED TENSORS of the node:
+        # autograd frees them when the graph is released — right after the backward, or, with `retain_graph=True`, when the graph dies —
+        # and a second backward through a released graph raises autograd's own error, as with the Inria op this replaces.
+        ctx.save_for_backward(means3D, scales, rotations, sh, opac, viewm, projm, campos, bg, radii, sh_rest, *frame.saved())
+        ctx.state, ctx.frame, ctx.backwards_run = state, frame, 0
         return out, radii
 
     @staticmethod
     @_guarded(0)
     def backward(ctx, v_out, _v_radii):
         import ctypes
-        means3D, scales, rotations, sh, opac, viewm, projm, campos, bg, radii, sh_rest, *frame_buffers = ctx.saved_tensors      # (a released graph raises here)
+        means3D, scales, rotations, sh, opac, viewm, projm, campos, bg, radii, sh_rest, *saved_blocks = ctx.saved_tensors      # (a released graph raises here)
+        blocks = ctx.frame.unpack(saved_blocks)
         H, W, degree, n_coeffs, tanfovx, tanfovy, scale_modifier, has_precomp_colors, use_cov, opac_shape, D = ctx.cfg
         prow = 6 + D      # the packed row: x y | a b c | opacity | colour (| 1/z)
         N = means3D.shape[0]
@@ -318,22 +273,15 @@ class _InriaFusedFn(torch.autograd.Function):
         ctx.backwards_run += 1
         if ctx.backwards_run > 1 and ctx.state.seg_ckpt:
             # retain_graph: the segmented backward counts the segments it publishes in two words the FORWARD kernel cleared — clear them again
-            for t in frame_buffers:
-                if t.data_ptr() <= ctx.state.seg_words < t.data_ptr() + t.numel():
-                    _view(t.data, ctx.state.seg_words, (2,), torch.int32).zero_()      # (.data: the saved tensor's version counter must not move)
+            blocks.view(ctx.state.seg_words, (2,), torch.int32).zero_()
         v_out = _grad_or_zeros(v_out, (D, H, W), dev)
         E = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        packed = None
-        if ctx.packed_at:      # the block the forward's compositing kernel cleared (GSPL_INRIA_PACKED_READY): the C side clears nothing
-            for t in frame_buffers:
-                if t.data_ptr() == ctx.packed_at:
-                    packed = _view(t.data, ctx.packed_at, (N, prow), torch.float32)
-                    if ctx.backwards_run > 1:
-                        packed.zero_()      # retain_graph: the rows hold the first backward's sums
-        if packed is None:
+        if ctx.state.flags & L.GSPL_INRIA_PACKED_READY:      # the block the forward's compositing kernel cleared: the C side clears nothing
+            packed = blocks.view(ctx.frame.addresses[L.GSPL_BUF_PACKED], (N, prow), torch.float32)
+            if ctx.backwards_run > 1:
+                packed.zero_()      # retain_graph: the rows hold the first backward's sums
+        else:
             packed = E(N, prow)
-            if ctx.packed_at:
-                raise RuntimeError("GaussianRasterizer: the forward's packed block is gone")
         hit = torch.empty((N,), dtype=torch.uint8, device=dev) if S.track_hit_pixels else None
         # the density controller's statistics of THIS frame (density.request_stats_in_backward: the request names the radii this
         # forward returned): the preprocess-backward kernel applies them, once

@@ -14,7 +14,7 @@ from torch import Tensor
 
 from .. import _lib as L
 from ._common import _guarded, _f32c, _grad_or_zeros
-from . import inria as _inria      # the allocation call-back (looked up per call: tests wrap it with guard bands)
+from ._frame import FrameBlocks
 
 
 class SurfelRasterizationSettings(NamedTuple):
@@ -58,24 +58,12 @@ class _SurfelRasterizeFn(torch.autograd.Function):
         out = torch.empty((3, H, W), dtype=torch.float32, device=dev)
         allmap = torch.empty((7, H, W), dtype=torch.float32, device=dev)
         state = L.SurfelState()
-        holder = {"device": dev}
-        _inria._ALLOC_TLS.holder = holder
-        try:
+        with FrameBlocks(dev) as frame:
             L.call("gspl_rasterize_surfel_fwd", N, int(s.sh_degree), n_coeffs, L.ptr(means3D), L.ptr(scales), L.ptr(rotations), L.ptr(sh),
                    L.ptr(colors_precomp), L.ptr(opac), L.ptr(viewm), L.ptr(projm), L.ptr(campos), L.ptr(bg), W, H, float(s.scale_modifier),
-                   _inria._ALLOC_CB, None, L.ptr(out), L.ptr(allmap), L.ptr(radii), ctypes.byref(state), L.stream())
-        except RuntimeError:
-            if "error" in holder:
-                raise holder["error"]
-            raise
-        finally:
-            _inria._ALLOC_TLS.holder = None
-        holder.pop(L.GSPL_BUF_BINNING, None)
-        holder.pop(L.GSPL_BUF_LISTS_WORK, None)
-        holder.pop("error", None)
-        frame_buffers = [t for tag, ts in holder.items() if isinstance(ts, list) for t in ts]
-        ctx.save_for_backward(means3D, scales, rotations, sh, viewm, projm, campos, bg, radii, *frame_buffers)
-        ctx.state = state
+                   frame.callback, None, L.ptr(out), L.ptr(allmap), L.ptr(radii), ctypes.byref(state), L.stream())
+        ctx.save_for_backward(means3D, scales, rotations, sh, viewm, projm, campos, bg, radii, *frame.saved())
+        ctx.state, ctx.frame = state, frame
         ctx.cfg = (int(s.sh_degree), n_coeffs, float(s.scale_modifier), colors_precomp is not None, opacities.shape, scales.shape)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(radii)
@@ -84,7 +72,8 @@ class _SurfelRasterizeFn(torch.autograd.Function):
     @staticmethod
     @_guarded(0)
     def backward(ctx, v_out, _v_radii, v_allmap):
-        means3D, scales, rotations, sh, viewm, projm, campos, bg, radii = ctx.saved_tensors[:9]
+        means3D, scales, rotations, sh, viewm, projm, campos, bg, radii, *saved_blocks = ctx.saved_tensors
+        ctx.frame.unpack(saved_blocks)      # (the state points into them: they must not have moved)
         degree, n_coeffs, scale_modifier, has_precomp, opac_shape, scales_shape = ctx.cfg
         st = ctx.state
         N, H, W = st.N, st.height, st.width
@@ -100,19 +89,11 @@ class _SurfelRasterizeFn(torch.autograd.Function):
         v_sh = None if has_precomp else torch.empty_like(sh)
         v_cp = torch.empty((N, 3), dtype=torch.float32, device=dev) if has_precomp else None
         if N > 0:
-            holder = {"device": dev}
-            _inria._ALLOC_TLS.holder = holder
-            try:
+            with FrameBlocks(dev) as scratch:      # (the deterministic mode's per-entry rows: scratch of this call)
                 L.call("gspl_rasterize_surfel_bwd", degree, n_coeffs, L.ptr(means3D), L.ptr(scales), L.ptr(rotations), L.ptr(sh), L.ptr(viewm),
                        L.ptr(projm), L.ptr(campos), L.ptr(bg), scale_modifier, L.ptr(radii), ctypes.byref(st), L.ptr(v_out), L.ptr(v_allmap),
-                       _inria._ALLOC_CB, None, L.ptr(v_rows), L.ptr(v_means), L.ptr(v_means2d), L.ptr(v_sh), L.ptr(v_cp), L.ptr(v_opac),
+                       scratch.callback, None, L.ptr(v_rows), L.ptr(v_means), L.ptr(v_means2d), L.ptr(v_sh), L.ptr(v_cp), L.ptr(v_opac),
                        L.ptr(v_scales), L.ptr(v_rot), L.stream())
-            except RuntimeError:
-                if "error" in holder:
-                    raise holder["error"]
-                raise
-            finally:
-                _inria._ALLOC_TLS.holder = None
         # order: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, settings
         return v_means, v_means2d, v_sh, v_cp, v_opac.reshape(opac_shape), v_scales.reshape(scales_shape), v_rot, None
 

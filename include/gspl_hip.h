@@ -380,8 +380,9 @@ int gspl_inria_preprocess_bwd(int N, int degree, int n_coeffs,
  *    frame (waited for INSIDE the call), compositing.  Memory comes from the caller through `alloc` — the Inria library's own
  *    resize-call-back pattern: the returned device pointers must stay valid until the matching backward has run (the Python
  *    side keeps the torch byte tensors in the autograd context).  Tags tell the call-back what a block is for; one block per tag
- *    and call, except GSPL_BUF_LISTS_WORK which may be asked for twice (speculative emission with `capacity_hint` = a guess of
- *    the list length, e.g. the previous frame's x 1.25; 0 = no speculation).  No hipMalloc, no global state.
+ *    and call, except GSPL_BUF_LISTS_WORK, GSPL_BUF_LISTS and GSPL_BUF_CHECKPOINTS, which are asked for a second time when the
+ *    speculative emission's guess of the list length (`capacity_hint`, e.g. the previous frame's x 1.25; 0 = no speculation)
+ *    was too low: the second block replaces the first.  No hipMalloc, no global state.
  *    out_color [3,H,W], radii [N] are caller-allocated outputs; `state` receives the pointers the backward needs and
  *    n_isects (the list length — feed it back as the next frame's hint); its `flags` field is read BEFORE it is filled.
  * ---------------------------------------------------------------------------------------- */

@@ -355,3 +355,32 @@ def assert_pipeline_attributed(mode, r, W, H, bg, render, pairs, opacities=None,
     for name, got, ref in pairs:
         assert_close_attributed(got, ref, rel, name, rows, slack=None if slack is None else slack.get(name), **kw)
     return rows, frag
+
+
+def guard_library_blocks(monkeypatch, guard=4096, fill=None):
+    """Every block the library asks its allocation call-back for (`ops._frame.allocate`) handed out between two bands of 0xA5, `guard`
+    bytes each (the inner block stays 256-byte aligned, as torch's own blocks are), and pre-filled with `fill` when one is given.
+    Returns the list of (tag, bytes, outer block) handed out, for `check_guard_bands`."""
+    from gspl_amd.ops import _frame
+    outers = []
+
+    def allocate(nbytes, device, tag):
+        size = ((nbytes + 255) // 256 * 256 + 2 * guard,)
+        outer = torch.empty(size, dtype=torch.uint8, device=device) if fill is None else torch.full(size, fill, dtype=torch.uint8, device=device)
+        outer[:guard] = 0xA5
+        outer[guard + nbytes:] = 0xA5
+        outers.append((tag, nbytes, outer))
+        return outer[guard:guard + nbytes]
+
+    monkeypatch.setattr(_frame, "allocate", allocate)
+    return outers
+
+
+def check_guard_bands(outers, what, guard=4096):
+    """Both bands of every block `guard_library_blocks` handed out are intact; returns how many blocks there were."""
+    torch.cuda.synchronize()
+    assert outers, f"{what}: nothing was allocated through the call-back"
+    for tag, n, outer in outers:
+        assert bool((outer[:guard] == 0xA5).all()), f"{what}: a write BELOW block {tag} ({n} bytes)"
+        assert bool((outer[guard + n:] == 0xA5).all()), f"{what}: a write ABOVE block {tag} ({n} bytes)"
+    return len(outers)

@@ -8,7 +8,7 @@ import torch
 
 from oracle import gsplat_oracle as O
 import accel_oracle as A
-from hip_helpers import cov2d_condition, cov_chain_slack, footprint_slack
+from hip_helpers import check_guard_bands, cov2d_condition, cov_chain_slack, footprint_slack, guard_library_blocks
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -84,39 +84,6 @@ def test_metric_point_S_1080p_1M_locked_both_switches():
         ops.KEEP_LAST_RASTER = False
 
 
-def _allocator(monkeypatch, fill):
-    from gspl_amd import _lib as L
-    from gspl_amd.ops import inria
-    outers = []
-
-    def guarded(_ctx, tag, nbytes):
-        holder = inria._ALLOC_TLS.holder
-        try:
-            n = max(int(nbytes), 1)
-            n_up = (n + 255) // 256 * 256
-            outer = torch.full((n_up + 2 * GUARD,), fill, dtype=torch.uint8, device=holder["device"])
-            outer[:GUARD] = 0xA5
-            outer[GUARD + n:] = 0xA5
-            inner = outer[GUARD:GUARD + n]
-            holder.setdefault(tag, []).append(inner)
-            outers.append((tag, n, outer))
-            return inner.data_ptr()
-        except Exception as e:      # noqa: BLE001
-            holder["error"] = e
-            return 0
-
-    monkeypatch.setattr(inria, "_ALLOC_CB", L.ALLOC_FN(guarded))
-    return outers
-
-
-def _check(outers, what):
-    torch.cuda.synchronize()
-    for tag, n, outer in outers:
-        assert bool((outer[:GUARD] == 0xA5).all()), f"{what}: a write BELOW block {tag} ({n} bytes)"
-        assert bool((outer[GUARD + n:] == 0xA5).all()), f"{what}: a write ABOVE block {tag} ({n} bytes)"
-    return len(outers)
-
-
 # (the segmentation is FIXED per case — off or "always" — so that the two pre-fills run the same code path: the adaptive mode may switch
 # between the two forms from one frame to the next, and the segmented forward sums the colour per segment, a different rounding)
 @pytest.mark.parametrize("workload,segmented", [("S-smoke-surfaces", "always"), ("S-smoke", False), ("S-1080p-1M-surfaces", "always")])
@@ -134,7 +101,7 @@ def test_guard_bands_and_prefills_with_both_switches(monkeypatch, workload, segm
     wimg = torch.randn(4, H, W, generator=torch.Generator().manual_seed(2)).to(DEV)
     images = {}
     for fill in (0xFF, 0x00):
-        outers = _allocator(monkeypatch, fill)
+        outers = guard_library_blocks(monkeypatch, GUARD, fill)
         images[fill] = []
         for k in (0, 0, 5):
             del outers[:]
@@ -143,7 +110,7 @@ def test_guard_bands_and_prefills_with_both_switches(monkeypatch, workload, segm
             img, radii, inv = ops.rasterize_inria_accel(_settings(cams[k], W, H, bg), m, torch.zeros_like(m, requires_grad=True), o, c, scales=s,
                                                         rotations=q, antialiasing=True, inverse_depth=True)
             (torch.cat([img, inv]) * wimg).sum().backward()
-            assert _check(outers, f"{workload} view {k} fill {fill:#x}") >= 4
+            assert check_guard_bands(outers, f"{workload} view {k} fill {fill:#x}", GUARD) >= 4
             assert all(bool(torch.isfinite(t.grad).all()) for t in leaves)
             images[fill].append(torch.cat([img, inv]).detach())
     for a, b in zip(images[0xFF], images[0x00]):

@@ -8,44 +8,12 @@ import sys
 import pytest
 import torch
 
+from hip_helpers import check_guard_bands, guard_library_blocks
+
 pytestmark = pytest.mark.gpu
 
 GUARD = 4096
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tools"))
-
-
-def _guarded_allocator(monkeypatch):
-    from gspl_amd import _lib as L
-    from gspl_amd.ops import inria
-    outers = []
-
-    def guarded(_ctx, tag, nbytes):
-        holder = inria._ALLOC_TLS.holder
-        try:
-            n = max(int(nbytes), 1)
-            n_up = (n + 255) // 256 * 256            # (the inner block stays 256-byte aligned, as torch's own blocks are)
-            outer = torch.empty((n_up + 2 * GUARD,), dtype=torch.uint8, device=holder["device"])
-            outer[:GUARD] = 0xA5
-            outer[GUARD + n:] = 0xA5
-            inner = outer[GUARD:GUARD + n]
-            holder.setdefault(tag, []).append(inner)
-            outers.append((tag, n, outer))
-            return inner.data_ptr()
-        except Exception as e:      # noqa: BLE001
-            holder["error"] = e
-            return 0
-
-    monkeypatch.setattr(inria, "_ALLOC_CB", L.ALLOC_FN(guarded))
-    return outers
-
-
-def _check(outers, what):
-    torch.cuda.synchronize()
-    assert outers, "the fused call did not allocate through the call-back"
-    for tag, n, outer in outers:
-        assert bool((outer[:GUARD] == 0xA5).all()), f"{what}: a write BELOW block {tag} ({n} bytes)"
-        assert bool((outer[GUARD + n:] == 0xA5).all()), f"{what}: a write ABOVE block {tag} ({n} bytes)"
-    return len(outers)
 
 
 @pytest.mark.parametrize("segmented", [True, "always"])
@@ -53,7 +21,7 @@ def test_no_write_outside_the_blocks_of_the_fused_call(monkeypatch, segmented):
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     import fuzz_parity as FP
     from gspl_amd.ops._state import STATE as S
-    outers = _guarded_allocator(monkeypatch)
+    outers = guard_library_blocks(monkeypatch, GUARD)
     monkeypatch.setattr(S, "segmented_backward", segmented)
     hip, dev = FP.hip, FP.dev
     blocks = 0
@@ -70,7 +38,7 @@ def test_no_write_outside_the_blocks_of_the_fused_call(monkeypatch, segmented):
                                                    campos=cam["camera_center"].to(dev))
             img, radii = hip.GaussianRasterizer(st)(means3D=m, means2D=torch.zeros_like(m, requires_grad=True), opacities=o, shs=c, scales=s, rotations=q)
             (img * wimg.to(dev)).sum().backward()
-            blocks += _check(outers, f"seed {seed} {desc} frame {frame}")
+            blocks += check_guard_bands(outers, f"seed {seed} {desc} frame {frame}", GUARD)
     assert blocks > 400
 
 
@@ -81,7 +49,7 @@ def test_no_write_outside_the_blocks_at_the_metric_size(monkeypatch, workload, s
     import gspl_amd  # noqa: F401
     from gspl_amd import ops, synthetic
     from gspl_amd.ops._state import STATE as S
-    outers = _guarded_allocator(monkeypatch)
+    outers = guard_library_blocks(monkeypatch, GUARD)
     monkeypatch.setattr(S, "segmented_backward", segmented)
     wl = synthetic.WORKLOADS[workload]
     W, H = wl["width"], wl["height"]
@@ -100,5 +68,5 @@ def test_no_write_outside_the_blocks_at_the_metric_size(monkeypatch, workload, s
                                                campos=cam["camera_center"].to(dev))
         img, radii = ops.GaussianRasterizer(st)(means3D=m, means2D=torch.zeros_like(m, requires_grad=True), opacities=o, shs=c, scales=s, rotations=q)
         (img * wimg).sum().backward()
-        assert _check(outers, f"{workload} view {k}") >= 4
+        assert check_guard_bands(outers, f"{workload} view {k}", GUARD) >= 4
         assert all(bool(torch.isfinite(t.grad).all()) for t in leaves)

@@ -1120,6 +1120,38 @@ def test_a_second_backward_through_a_retained_graph(hip, segmented):
         hip.SEGMENTED_BACKWARD = saved
 
 
+@pytest.mark.parametrize("rasterizer", ["GaussianRasterizer", "SurfelGaussianRasterizer"])
+def test_a_backward_under_saved_tensor_hooks_refuses_moved_blocks(hip, rasterizer):
+    """The frame's device blocks are saved tensors of the node, and the rasterizer's state holds raw addresses into them.  Saved-tensor
+    hooks (`save_on_cpu`, non-reentrant checkpointing) hand the backward copies at other addresses while the originals go back to the
+    allocator: the backward refuses them before it launches anything.  The same frame without hooks back-propagates."""
+    if rasterizer == "GaussianRasterizer" and not hip.FUSED_INRIA:
+        pytest.skip("GSPL_FUSED_INRIA=0")
+    means, scales, quats, opac, shs, cam, wimg, bg = _e2e_scene(n=3000, seed=46)
+    W, H = cam["width"], cam["height"]
+    settings = _inria_settings(hip, cam, bg, W, H)
+    if rasterizer == "SurfelGaussianRasterizer":
+        settings, scales = hip.SurfelRasterizationSettings(*settings), scales[:, :2]
+
+    def frame():
+        leaves = [t.requires_grad_(True) for t in _cuda(means, scales, quats, opac, shs)]
+        m, s, q, o, c = leaves
+        out = getattr(hip, rasterizer)(settings)(means3D=m, means2D=torch.zeros_like(m, requires_grad=True), opacities=o, shs=c, scales=s, rotations=q)
+        return leaves, (out[0] * wimg.to(_dev())).sum()
+
+    hooks = torch.autograd.graph.save_on_cpu()
+    originals = []      # (kept allocated: no copy can get its original's address back, where the move would go unnoticed — harmlessly)
+    pack = hooks.pack_hook
+    hooks.pack_hook = lambda t: (originals.append(t), pack(t))[1]
+    with hooks:
+        leaves, loss = frame()
+    with pytest.raises(RuntimeError, match="saved-tensor hooks"):
+        loss.backward()
+    leaves, loss = frame()
+    loss.backward()
+    assert all(bool(torch.isfinite(t.grad).all()) for t in leaves) and float(leaves[0].grad.abs().sum()) > 0
+
+
 def test_degenerate_inputs(hip):
     """Everything behind the camera, a single huge splat covering the whole image, image smaller than a tile."""
     d = _dev()

@@ -145,10 +145,11 @@ def test_hip_vanilla_renderer_raw_parameters_activations_inside_the_kernels(scal
                                opacities=torch.sigmoid(raw64["opacities"]).reshape(-1), gpu_radii=out_f["radii"])
 
 
-def test_raw_parameters_need_a_zeroed_state_and_the_scale_rotation_pair():
+def test_raw_parameters_need_a_zeroed_state_and_the_scale_rotation_pair(monkeypatch):
     import ctypes
     import gspl_amd  # noqa: F401
     from gspl_amd import _lib as L, ops
+    from gspl_amd.ops import _frame
     params, cam, wimg, bg = _scene(n=500)
     m, s, q, o, sh = [p.to(DEV) for p in params]
     settings = ops.GaussianRasterizationSettings(cam["height"], cam["width"], cam["tanfovx"], cam["tanfovy"], bg.to(DEV), 1.0,
@@ -160,11 +161,15 @@ def test_raw_parameters_need_a_zeroed_state_and_the_scale_rotation_pair():
     state = L.InriaState()
     state.flags = 64
     out, radii = torch.empty(3, cam["height"], cam["width"], device=DEV), torch.empty(500, dtype=torch.int32, device=DEV)
-    cb = L.ALLOC_FN(lambda ctx, tag, n: 0)
-    with pytest.raises(Exception, match="flags"):
+
+    def refuse(nbytes, device, tag):      # (a block asked for before the refusal would end the call with this error instead)
+        raise MemoryError("no block")
+
+    monkeypatch.setattr(_frame, "allocate", refuse)
+    with pytest.raises(Exception, match="flags"), _frame.FrameBlocks(DEV) as frame:
         L.call("gspl_rasterize_inria_fwd", 500, 3, 16, L.ptr(m), L.ptr(s), L.ptr(q), None, L.ptr(sh), None, None, L.ptr(o),
                L.ptr(settings.viewmatrix), L.ptr(settings.projmatrix), L.ptr(settings.campos), L.ptr(settings.bg), cam["width"], cam["height"],
-               float(cam["tanfovx"]), float(cam["tanfovy"]), 1.0, cb, None, 0, L.ptr(out), L.ptr(radii), ctypes.byref(state), L.stream(), None)
+               float(cam["tanfovx"]), float(cam["tanfovy"]), 1.0, frame.callback, None, 0, L.ptr(out), L.ptr(radii), ctypes.byref(state), L.stream(), None)
 
 
 def test_config1_lego_proxy_800x800_100k_vanilla_renderer_vs_oracle():

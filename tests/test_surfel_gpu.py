@@ -138,26 +138,8 @@ GUARD = 4096
 @pytest.mark.parametrize("fill", [0xFF, 0x00])
 def test_surfel_guard_bands(monkeypatch, fill):
     from gspl_amd import _lib as L
-    from gspl_amd.ops import inria
-    outers = []
-
-    def guarded(_ctx, tag, nbytes):
-        holder = inria._ALLOC_TLS.holder
-        try:
-            n = max(int(nbytes), 1)
-            n_up = (n + 255) // 256 * 256
-            outer = torch.full((n_up + 2 * GUARD,), fill, dtype=torch.uint8, device=holder["device"])
-            outer[:GUARD] = 0xA5
-            outer[GUARD + n:] = 0xA5
-            inner = outer[GUARD:GUARD + n]
-            holder.setdefault(tag, []).append(inner)
-            outers.append((tag, n, outer))
-            return inner.data_ptr()
-        except Exception as e:      # noqa: BLE001
-            holder["error"] = e
-            return 0
-
-    monkeypatch.setattr(inria, "_ALLOC_CB", L.ALLOC_FN(guarded))
+    from hip_helpers import check_guard_bands, guard_library_blocks
+    outers = guard_library_blocks(monkeypatch, GUARD, fill)
     params, cam = _special_scene(seed=8)
     gen = torch.Generator().manual_seed(1)
     v_color, v_allmap = torch.randn(3, H, W, generator=gen), torch.randn(7, H, W, generator=gen)
@@ -172,9 +154,7 @@ def test_surfel_guard_bands(monkeypatch, fill):
         assert all(bool(torch.isfinite(g).all()) for g in grads.values())
     tags = {t for t, _, _ in outers}
     assert {L.GSPL_BUF_GEOMETRY, L.GSPL_BUF_IMAGE, L.GSPL_BUF_BINNING, L.GSPL_BUF_LISTS_WORK, L.GSPL_BUF_LISTS, L.GSPL_BUF_SURFEL_ENTRIES} <= tags
-    for tag, n, outer in outers:
-        band = torch.cat([outer[:GUARD], outer[GUARD + n:]])
-        assert bool((band == 0xA5).all()), f"guard band of tag {tag} ({n} bytes) overwritten"
+    check_guard_bands(outers, "surfel", GUARD)
     # the pre-fill of the blocks does not leak into the results
     ref = _run_hip(params, cam, torch.tensor([0.1, 0.2, 0.3]), 1.0, "shs", v_color, v_allmap)
     assert torch.equal(ref[0], results[0][0]) and torch.equal(ref[2], results[0][1])
