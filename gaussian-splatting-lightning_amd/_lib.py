@@ -9,184 +9,122 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 import subprocess
-from ctypes import c_float, c_int, c_int64, c_size_t, c_void_p
+from ctypes import c_float, c_int, c_void_p
 
 import torch
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSPL_HIP_LIB", os.path.join(_PKG_DIR, "libgspl_hip.so"))   # override: A/B builds of the same ABI
-ABI_VERSION = 39
-
-GSPL_RECORD_FLOATS = 12
-GSPL_CAMERA_PINHOLE, GSPL_CAMERA_ORTHO, GSPL_CAMERA_FISHEYE = 0, 1, 2
-CAMERA_MODELS = {"pinhole": 0, "ortho": 1, "fisheye": 2}
-GSPL_MODE_GSPLAT = 0
-GSPL_MODE_INRIA = 1
-GSPL_LAYOUT_HWC = 0
-GSPL_LAYOUT_CHW = 1
-GSPL_SH_ADD_HALF_CLAMP = 1
-GSPL_INRIA_GEOMETRY, GSPL_INRIA_COLOURS, GSPL_INRIA_ALL = 1, 2, 3
-GSPL_INRIA_RAW_PARAMS = 1      # gspl_inria_state.flags: scales / rotations / opacities are the model's raw parameters
-GSPL_INRIA_NO_SEGMENTS = 2     # ... never segment the backward (the plain one-workgroup-per-tile walk)
-GSPL_INRIA_FORCE_SEGMENTS = 4  # ... always (default: adaptively, while walks longer than a segment are being met)
-GSPL_INRIA_WILL_BACKWARD = 8   # ... IN: a backward follows: the forward clears the backward's packed rows (GSPL_BUF_PACKED)
-GSPL_INRIA_PACKED_READY = 16   # ... OUT: it did
-GSPL_INRIA_ANTIALIAS = 32      # ... IN (ABI 36): opacity * sqrt(max(2.5e-5, det0 / det1)), the Mip-Splatting 2D filter
-GSPL_INRIA_INVDEPTH = 128      # ... IN (ABI 36): a 4th composited channel, 1 / z (out [4,H,W], bg of 4 values, packed rows of 10)
-GSPL_BIN_SPAN_BYTES = 64
-GSPL_ADAM_MAX_TENSORS = 16
-
-
-class AdamTensor(ctypes.Structure):
-    """`gspl_adam_tensor` of include/gspl_hip.h."""
-    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
-                ("exp_avg_sq", ctypes.c_void_p), ("lr", ctypes.c_float), ("row_elems", ctypes.c_int32)]
-
-
-class BwdAdamTensor(ctypes.Structure):
-    """`gspl_bwd_adam_tensor` of include/gspl_hip.h (moments + hyper-parameters of one parameter updated inside the backward)."""
-    _fields_ = [("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p), ("lr", ctypes.c_float), ("beta1", ctypes.c_float),
-                ("beta2", ctypes.c_float), ("eps", ctypes.c_float), ("bias_correction1", ctypes.c_float), ("bias_correction2_sqrt", ctypes.c_float)]
-
-
-class BwdAdamPlan(ctypes.Structure):
-    """`gspl_bwd_adam_plan`."""
-    _fields_ = [(n, BwdAdamTensor) for n in ("means", "scales", "rotations", "opacities", "shs", "shs_rest")]
+HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), "include", "gspl_hip.h")         # the in-tree header, also for an overridden library
 
 
 class HipLibraryError(RuntimeError):
     pass
 
 
-# `gspl_alloc_fn` / `gspl_inria_state` of include/gspl_hip.h (the fused Inria entry points)
-GSPL_BUF_GEOMETRY, GSPL_BUF_BINNING, GSPL_BUF_IMAGE, GSPL_BUF_LISTS_WORK, GSPL_BUF_LISTS, GSPL_BUF_CHECKPOINTS, GSPL_BUF_PACKED = 1, 2, 3, 4, 5, 6, 7
-GSPL_BUF_SURFEL_ENTRIES = 8    # (ABI 37) the deterministic surfel backward's per-list-entry rows
-ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t)
+# The binding is READ from the header when this module is imported: entry points, constants and structs are written down once, in
+# include/gspl_hip.h.  The parser knows exactly the C the header uses; whatever it cannot classify raises.
+_SCALARS = {"int": c_int, "float": c_float, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64,
+            "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "uint8_t": ctypes.c_uint8}
+_RETURNS = {"int": c_int, "size_t": ctypes.c_size_t, "void*": c_void_p, "const char*": ctypes.c_char_p}
+_DECLARATION = re.compile(r"(?:const\s+)?(\w+)(\s+|\s*(?:\*\s*(?:const\b\s*)?)+)(\w+)")
 
 
-class InriaState(ctypes.Structure):
-    _fields_ = [("N", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int), ("n_isects", ctypes.c_int64),
-                ("means2d", ctypes.c_void_p), ("depths", ctypes.c_void_p), ("conics", ctypes.c_void_p), ("colors", ctypes.c_void_p),
-                ("clamped", ctypes.c_void_p), ("cov3d", ctypes.c_void_p), ("sh_jac", ctypes.c_void_p),
-                ("alphas", ctypes.c_void_p), ("final_Ts", ctypes.c_void_p), ("last_ids", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
-                ("flatten_ids", ctypes.c_void_p), ("opacities", ctypes.c_void_p), ("flags", ctypes.c_int),
-                ("seg_ckpt", ctypes.c_void_p), ("seg_words", ctypes.c_void_p), ("seg_slots", ctypes.c_uint32), ("seg_reserved", ctypes.c_uint32),
-                ("stats_accum", ctypes.c_void_p), ("stats_denom", ctypes.c_void_p), ("stats_max_radii", ctypes.c_void_p)]
+def _unparsed(what, why="cannot classify"):
+    raise HipLibraryError(f"gspl_hip.h: {why} `{' '.join(what.split())}`")
 
 
-class SurfelState(ctypes.Structure):
-    """`gspl_surfel_state` of include/gspl_hip.h (section 6c, the 2DGS rasterizer)."""
-    _fields_ = [("N", ctypes.c_int), ("width", ctypes.c_int), ("height", ctypes.c_int), ("n_isects", ctypes.c_int64),
-                ("rec", ctypes.c_void_p), ("means2d", ctypes.c_void_p), ("depths", ctypes.c_void_p), ("colors", ctypes.c_void_p),
-                ("clamped", ctypes.c_void_p), ("final_T", ctypes.c_void_p), ("M1", ctypes.c_void_p), ("M2", ctypes.c_void_p),
-                ("last_contrib", ctypes.c_void_p), ("median_contrib", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
-                ("flatten_ids", ctypes.c_void_p)]
+def _ctype(decl, types, where):
+    """`[const] type[*...] name` -> (ctypes type, name); `types`: the structs and function-pointer typedefs declared so far."""
+    m = _DECLARATION.fullmatch(decl.strip())
+    if not m:
+        _unparsed(decl, f"{where}: cannot parse the declaration")
+    base, stars, name = m[1], m[2].count("*"), m[3]
+    known = types.get(base, _SCALARS.get(base))
+    if stars == 0 and known is not None:
+        return known, name
+    if stars == 1 and isinstance(known, type) and issubclass(known, ctypes.Structure):
+        return ctypes.POINTER(known), name      # (the wrong struct raises; an array of the struct is accepted)
+    if stars and (base == "void" or base in _SCALARS):
+        return c_void_p, name
+    _unparsed(decl, f"{where}: unknown type in")
 
 
-_P = c_void_p
-_SIGNATURES = {
-    # name: (restype, argtypes)
-    "gspl_abi_version": (c_int, []),
-    "gspl_last_error": (ctypes.c_char_p, []),
-    "gspl_composite_bwd_kernel_name": (ctypes.c_char_p, []),
-    "gspl_set_deterministic": (c_int, [c_int]),
-    "gspl_get_deterministic": (c_int, []),
-    "gspl_project_fwd": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int,
-                                 c_float, c_float, c_float, c_float, c_float, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "gspl_project_bwd": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_float, c_int,
-                                 _P, _P, c_int, _P, _P, c_int, _P, _P, _P, _P, _P]),
-    "gspl_low_priority_stream": (c_void_p, []),
-    "gspl_records_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "gspl_records_pack_fwd": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "gspl_records_count_fwd": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "gspl_records_scatter_fwd": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "gspl_records_pad_fwd": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "gspl_records_pack_bwd": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "gspl_records_unpack_fwd": (c_int, [ctypes.c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "gspl_records_unpack_bwd": (c_int, [ctypes.c_int64, c_int, _P, _P, c_int, _P, _P, c_int, _P, c_int, _P, c_int, _P, _P]),
-    "gspl_peer_alloc": (c_int, [c_size_t, _P, _P]),
-    "gspl_peer_open": (c_int, [_P, _P]),
-    "gspl_peer_close": (c_int, [_P]),
-    "gspl_peer_free": (c_int, [_P]),
-    "gspl_peer_put_rows": (c_int, [c_int, _P, _P, _P, c_int, _P]),
-    "gspl_peer_signal": (c_int, [c_int, _P, ctypes.c_uint64, _P]),
-    "gspl_peer_wait": (c_int, [_P, c_int, ctypes.c_uint64, ctypes.c_uint64, _P, _P]),
-    "gspl_sh_fwd": (c_int, [c_int, c_int, _P, _P, _P, c_int, _P, c_int, _P, c_int, _P, _P, _P]),
-    "gspl_sh_bwd": (c_int, [c_int, c_int, c_int, _P, _P, _P, c_int, _P, c_int, _P, c_int, _P, _P, c_int, _P, _P, _P, _P]),
-    "gspl_sh_fwd_batched": (c_int, [c_int, c_int, c_int, _P, _P, _P, c_int, _P, c_int, _P, c_int, _P, _P, _P]),
-    "gspl_sh_bwd_batched": (c_int, [c_int, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P]),
-    "gspl_isect_workspace_bytes": (c_size_t, [c_int, c_int64]),
-    "gspl_isect_count": (c_int, [c_int, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
-    "gspl_isect_emit_sort": (c_int, [c_int, c_int, _P, _P, _P, _P, c_int, c_int, c_int, c_int64, _P, _P, _P, c_size_t, _P]),
-    "gspl_isect_offsets": (c_int, [c_int64, _P, c_int, c_int, _P, _P]),
-    "gspl_bin_workspace_bytes": (c_size_t, [c_int, c_int64]),
-    "gspl_loss_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "gspl_loss_l1_ssim_fwd": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "gspl_loss_photometric_fwd": (c_int, [c_int, c_int, c_int, _P, _P, c_float, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "gspl_loss_l1_ssim_bwd": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, _P, _P]),
-    "gspl_selective_adam": (c_int, [c_int, _P, c_int, _P, c_float, c_float, c_float, c_float, c_float, _P]),
-    "gspl_selective_adam_limited": (c_int, [c_int, _P, c_int, _P, c_float, c_float, c_float, c_float, c_float, c_int, _P]),
-    "gspl_radix_sort_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
-    "gspl_radix_sort_pairs_u32": (c_int, [c_int64, _P, _P, _P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
-    "gspl_radix_sort_keys_u64": (c_int, [c_int64, _P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
-    "gspl_composite_scores": (c_int, [c_int, c_int64, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P,
-                                      _P, _P, _P, _P, _P, _P, _P]),
-    "gspl_densify_stats": (c_int, [c_int, _P, c_int, c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "gspl_densify_stats_views": (c_int, [c_int, c_int, _P, c_int, c_float, c_float, _P, _P, _P, _P, _P, _P, _P]),
-    "gspl_knn_workspace_bytes": (c_size_t, [c_int]),
-    "gspl_knn3_mean_dist2": (c_int, [c_int, _P, _P, _P, c_size_t, _P]),
-    "gspl_bin_count": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "gspl_bin_emit": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int64, _P, c_size_t, _P]),
-    "gspl_bin_sort": (c_int, [c_int, c_int, c_int, c_int64, c_int64, _P, _P, _P, c_size_t, _P]),
-    "gspl_bin_sort_device_count": (c_int, [c_int, c_int, c_int, _P, c_int64, _P, _P, _P, c_size_t, _P]),
-    "gspl_bin_emit_sort": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int64, _P, _P, _P, c_size_t, _P]),
-    "gspl_composite_fwd": (c_int, [c_int, c_int64, c_int, c_int, c_int, _P, _P, _P, _P, _P,
-                                   c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "gspl_composite_bwd": (c_int, [c_int, c_int64, c_int, c_int, c_int, _P, _P, _P, _P, _P,
-                                   c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P,
-                                   _P, _P, _P, _P, _P, _P, _P]),
-    "gspl_composite_bwd_packed": (c_int, [c_int, c_int64, c_int, c_int, c_int, _P, _P, _P, _P, _P,
-                                          c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
-    "gspl_inria_preprocess_fwd": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                          c_int, c_int, c_int, c_float, c_float, c_float,
-                                          _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),
-    "gspl_rasterize_inria_fwd": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_float, c_float,
-                                         ALLOC_FN, _P, c_int64, _P, _P, ctypes.POINTER(InriaState), _P, _P]),
-    "gspl_rasterize_inria_bwd": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, c_float,
-                                         _P, ctypes.POINTER(InriaState), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "gspl_rasterize_inria_bwd_adam": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, c_float,
-                                              _P, ctypes.POINTER(InriaState), _P, _P, _P, _P, _P, ctypes.POINTER(BwdAdamPlan), _P]),
-    "gspl_profile_enable": (c_int, [c_int]),
-    "gspl_profile_enable2": (c_int, [c_int, c_int]),
-    "gspl_profile_read": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_float)]),
-    "gspl_rasterize_inria_geometry_bytes": (c_size_t, [c_int]),
-    "gspl_rasterize_inria_image_bytes": (c_size_t, [c_int, c_int]),
-    "gspl_inria_state_bytes": (c_size_t, []),
-    "gspl_surfel_state_bytes": (c_size_t, []),
-    "gspl_rasterize_surfel_fwd": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_float,
-                                          ALLOC_FN, _P, _P, _P, _P, ctypes.POINTER(SurfelState), _P]),
-    "gspl_rasterize_surfel_bwd": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_float, _P, ctypes.POINTER(SurfelState), _P, _P,
-                                          ALLOC_FN, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "gspl_inria_preprocess_bwd": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                          c_int, c_int, c_float, c_float, c_float,
-                                          _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    # section 13 (ABI 38): the 3DGS-MCMC density controller (csrc/mcmc.hip)
-    "gspl_mcmc_relocation": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
-    "gspl_mcmc_perturb_means": (c_int, [c_int, c_int, _P, _P, _P, _P, _P, c_float, ctypes.c_uint64, ctypes.c_uint64, _P]),
-    "gspl_mcmc_randn": (c_int, [c_int, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P]),
-    "gspl_mcmc_reg_partials": (c_int, [c_int]),
-    "gspl_mcmc_reg_fwd": (c_int, [c_int, c_int, _P, _P, c_float, c_float, _P, _P, _P]),
-    "gspl_mcmc_reg_bwd": (c_int, [c_int, c_int, _P, _P, c_float, c_float, _P, _P, _P, _P]),
-    # section 14 (ABI 39): bilateral-grid slicing and its TV loss (csrc/bilagrid.hip)
-    "gspl_bilagrid_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "gspl_bilagrid_slice_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, c_int, _P, c_int, _P, _P]),
-    "gspl_bilagrid_slice_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P, c_int, _P, c_int, _P, c_int,
-                                        _P, _P, c_int, _P, c_size_t, _P]),
-    "gspl_bilagrid_tv_partials": (c_int, [c_int64]),
-    "gspl_bilagrid_tv_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
-    "gspl_bilagrid_tv_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
-}
+def _restype(text):
+    key = re.sub(r"\s*\*", "*", " ".join(text.split()))
+    return _RETURNS[key] if key in _RETURNS else _unparsed(text, "unknown return type")
+
+
+def _parameters(text, types, where):
+    return [] if text.strip() in ("", "void") else [_ctype(p, types, where) for p in text.split(",")]
+
+
+def _parse_header(text):
+    """-> (constants {name: int}, types {C name: Structure subclass | CFUNCTYPE}, functions {name: (restype, argtypes, parameter names)})."""
+    constants, types, functions, lines = {}, {}, {}, []
+    for line in re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S).splitlines():
+        define = re.fullmatch(r"\s*#\s*define\s+(\w+)\s*(.*?)\s*", line)
+        if define and define[2]:
+            constants[define[1]] = int(define[2]) if re.fullmatch(r"-?\d+", define[2]) else _unparsed(line)
+        elif not line.lstrip().startswith("#"):
+            lines.append(line)
+        elif not define and not re.match(r"\s*#\s*(include|ifdef|ifndef|endif)\b", line):
+            _unparsed(line)
+
+    def function_pointer(m):
+        types[m[2]] = ctypes.CFUNCTYPE(_restype(m[1]), *[t for t, _ in _parameters(m[3], types, m[2])])
+        return ""
+
+    def struct(m):
+        fields = []
+        for statement in filter(str.strip, m[2].split(";")):      # `int N, width, height`, `float* a`, `gspl_x means, scales`
+            first, *more = statement.split(",")
+            ctype, name = _ctype(first, types, m[1])
+            if m[1] != m[3] or (more and "*" in statement) or not all(re.fullmatch(r"\s*\w+\s*", n) for n in more):
+                _unparsed(statement, f"{m[1]}: cannot parse the field(s)")
+            fields += [(n.strip(), ctype) for n in [name] + more]
+        python_name = "".join(word.capitalize() for word in m[1][len("gspl_"):].split("_"))
+        types[m[1]] = type(python_name, (ctypes.Structure,), {"_fields_": fields, "__doc__": f"`{m[1]}` of include/gspl_hip.h."})
+        return ""
+
+    def enum(m):
+        for item in m[1].split(","):
+            entry = re.fullmatch(r"\s*(\w+)\s*=\s*(-?\d+)\s*", item) or _unparsed(item, "cannot parse the enumerator")
+            constants[entry[1]] = int(entry[2])
+        return ""
+
+    text = "\n".join(lines)
+    text = re.sub(r"typedef\s+([\w\s*]+?)\(\s*\*\s*(\w+)\s*\)\s*\(([^()]*)\)\s*;", function_pointer, text)
+    text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, text)
+    text = re.sub(r"enum\s*\{([^{}]*)\}\s*;", enum, text)
+    *prototypes, rest = re.sub(r'extern\s+"C"\s*\{', "", text).split(";")
+    if rest.strip() not in ("", "}"):
+        _unparsed(rest)
+    for prototype in prototypes:
+        m = re.fullmatch(r"\s*([\w\s*]+?)\s*\b(gspl_\w+)\s*\(([^()]*)\)\s*", prototype) or _unparsed(prototype)
+        args = _parameters(m[3], types, m[2])
+        functions[m[2]] = (_restype(m[1]), [t for t, _ in args], tuple(n for _, n in args))
+    return constants, types, functions
+
+
+def _read_header(path):
+    try:
+        with open(path) as f:
+            return _parse_header(f.read())
+    except OSError as e:
+        raise HipLibraryError(f"{path} not readable ({e}): the ctypes binding of this package is read from it; there is no other table") from e
+
+
+_CONSTANTS, _TYPES, _FUNCTIONS = _read_header(HEADER_PATH)
+globals().update({name: value for name, value in _CONSTANTS.items() if name.startswith("GSPL_")})      # every GSPL_* of the header
+ABI_VERSION = _CONSTANTS["GSPL_ABI_VERSION"]
+CAMERA_MODELS = {"pinhole": _CONSTANTS["GSPL_CAMERA_PINHOLE"], "ortho": _CONSTANTS["GSPL_CAMERA_ORTHO"], "fisheye": _CONSTANTS["GSPL_CAMERA_FISHEYE"]}
+ALLOC_FN = _TYPES["gspl_alloc_fn"]
+AdamTensor, BwdAdamTensor, BwdAdamPlan, InriaState, SurfelState = (
+    _TYPES[name] for name in ("gspl_adam_tensor", "gspl_bwd_adam_tensor", "gspl_bwd_adam_plan", "gspl_inria_state", "gspl_surfel_state"))
+_SIGNATURES = {name: (restype, argtypes) for name, (restype, argtypes, _) in _FUNCTIONS.items()}
 
 _LIB = None
 
@@ -231,7 +169,6 @@ def lib():
     got = handle.gspl_abi_version()
     if got != ABI_VERSION:
         raise HipLibraryError(f"ABI mismatch: library {got}, python binding {ABI_VERSION}; rebuild the extension")
-    handle.gspl_inria_state_bytes.restype = c_size_t
     if handle.gspl_inria_state_bytes() != ctypes.sizeof(InriaState):
         raise HipLibraryError(f"gspl_inria_state: the library's struct has {handle.gspl_inria_state_bytes()} bytes, the binding's "
                               f"{ctypes.sizeof(InriaState)}; rebuild the extension")
@@ -287,14 +224,19 @@ def call(name: str, *args):
         seen = _PROFILE_SEEN.get(name, 0)
         _PROFILE_SEEN[name] = seen + 1
         timed = seen % _PROFILE_PERIOD == 0
-    if timed:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        rc = fn(*args)
-        e1.record()
-        _PROFILE.append((name, e0, e1))
-    else:
-        rc = fn(*args)
+    try:
+        if timed:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            rc = fn(*args)
+            e1.record()
+            _PROFILE.append((name, e0, e1))
+        else:
+            rc = fn(*args)
+    except ctypes.ArgumentError as e:      # "argument 17: TypeError: ..." -> "gspl_x: argument 17 (v_rows): ..."
+        names = _FUNCTIONS[name][2]
+        named = re.sub(r"argument (\d+)", lambda m: f"argument {m[1]} ({names[int(m[1]) - 1]})" if int(m[1]) <= len(names) else m[0], str(e), count=1)
+        raise ctypes.ArgumentError(f"{name}: {named}") from e
     check(rc, name)
 
 

@@ -70,7 +70,7 @@ def update_densification_stats_views(grads, visibility_filters, radii, xyz_gradi
     n_views = len(grads)
     if n_views == 0:
         return
-    ok = 1 <= n_views <= 16 and all(isinstance(g, Tensor) and g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.dim() == 2 for g in grads)
+    ok = 1 <= n_views <= L.GSPL_STATS_MAX_VIEWS and all(isinstance(g, Tensor) and g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.dim() == 2 for g in grads)
     ok = ok and all(r is not None and r.dtype == torch.int32 and r.is_contiguous() and r.numel() == grads[0].shape[0] for r in radii)
     ok = ok and len({tuple(g.shape) for g in grads}) == 1 and (scale is None or isinstance(scale, (Tensor, float, int)))
     if not ok:

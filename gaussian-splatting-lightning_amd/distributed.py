@@ -27,7 +27,9 @@ import os
 import torch
 import torch.distributed as dist
 
-RECORD_FLOATS = 12     # 48 B per visible splat
+from . import _lib as L
+
+RECORD_FLOATS = L.GSPL_RECORD_FLOATS     # 48 B per visible splat
 # A group of one rank needs no exchange and the reductions below return at once.  False makes them issue their collectives
 # anyway: how tests/test_rccl_single_rank.py and `bench.py --init-dist` drive the RCCL code paths on a one-GPU machine.
 SINGLE_RANK_SHORTCUT = True
@@ -295,7 +297,6 @@ class PeerExchange:
         if self._mine is not None and total <= self.cap_total and biggest <= self.cap_rank:
             return
         import ctypes
-        from . import _lib as L
         self.close()
         self.cap_total, self.cap_rank = int(total * 1.5) + 1024, int(biggest * 1.5) + 1024
         self._layout = lay = self._plan(self.cap_total, self.cap_rank)
@@ -349,7 +350,6 @@ class PeerExchange:
         """Frees this rank's buffer and mappings without any collective (the failure path of `_ensure`)."""
         if self._mine is None and not self._opened:
             return
-        from . import _lib as L
         with torch.cuda.device(self.device):
             for p in self._opened:
                 L.lib().gspl_peer_close(p)
@@ -360,7 +360,6 @@ class PeerExchange:
     def close(self):
         if self._mine is None:
             return
-        from . import _lib as L
         torch.cuda.synchronize(self.device)
         if self.world > 1:
             dist.barrier(group=self.group)          # the peers are done with the old buffers
@@ -382,7 +381,6 @@ class PeerExchange:
     # ---- one exchange ---------------------------------------------------------------------------------------------------
     def _send(self, rows: torch.Tensor, begin: List[int], dst: List[int], flag_dst: List[int], my_flags: int, value: int):
         import ctypes
-        from . import _lib as L
         W = self.world
         rows = rows.contiguous()
         with torch.cuda.device(self.device):

@@ -167,7 +167,7 @@ class _FusedAdamBase(torch.optim.Optimizer):
                         raise RuntimeError("fused Adam: exp_avg / exp_avg_sq must be contiguous fp32 tensors of the parameter's shape")
                     table[k] = L.AdamTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), lr, row)
                 with torch.cuda.device(dev):
-                    L.call("gspl_selective_adam_limited", len(chunk), ctypes.cast(table, ctypes.c_void_p), N, L.ptr(vis),
+                    L.call("gspl_selective_adam_limited", len(chunk), table, N, L.ptr(vis),
                            float(b1), float(b2), float(eps), float(bc1), float(bc2s), int(max_blocks), L.stream())
 
     def _launch(self, visibility: Optional[torch.Tensor]):

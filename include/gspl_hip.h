@@ -53,6 +53,7 @@ enum { GSPL_CAMERA_PINHOLE = 0, GSPL_CAMERA_ORTHO = 1, GSPL_CAMERA_FISHEYE = 2 }
 enum { GSPL_LAYOUT_HWC = 0, GSPL_LAYOUT_CHW = 1 };
 
 /* ABI version, bumped on any signature change; checked by the ctypes loader. */
+#define GSPL_ABI_VERSION 39
 int gspl_abi_version(void);
 /* Human-readable description of the last launch error on this thread (never NULL). */
 const char* gspl_last_error(void);
