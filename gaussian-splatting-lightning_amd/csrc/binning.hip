@@ -22,25 +22,6 @@
 
 namespace gspl {
 
-// tile rectangle of one splat, per API convention
-template <int MODE>
-__device__ __forceinline__ void tile_rect(float x, float y, int radius, int tile_size, int tile_w, int tile_h,
-                                          int& minx, int& miny, int& maxx, int& maxy) {
-    const float ts = (float)tile_size;
-    const float r = (float)radius;
-    if (MODE == GSPL_MODE_GSPLAT) {
-        // gaussian_projection.py:117-125 : trunc((p - r)/T), trunc((p + r)/T) + 1
-        minx = (int)((x - r) / ts); miny = (int)((y - r) / ts);
-        maxx = (int)((x + r) / ts) + 1; maxy = (int)((y + r) / ts) + 1;
-    } else {
-        // Inria getRect: (int)((p - r)/T), (int)((p + r + T - 1)/T)
-        minx = (int)((x - r) / ts); miny = (int)((y - r) / ts);
-        maxx = (int)((x + r + ts - 1.f) / ts); maxy = (int)((y + r + ts - 1.f) / ts);
-    }
-    minx = min(max(minx, 0), tile_w); maxx = min(max(maxx, 0), tile_w);
-    miny = min(max(miny, 0), tile_h); maxy = min(max(maxy, 0), tile_h);
-}
-
 template <int MODE>
 __global__ __launch_bounds__(256) void isect_count_kernel(
     int N, const float* __restrict__ means2d, const int32_t* __restrict__ radii,
@@ -725,6 +706,28 @@ extern "C" int gspl_bin_emit_sort(int N, int mode, const float* means2d, const i
                            workspace, workspace_bytes, stream);
     if (rc != GSPL_OK) return rc;
     return gspl_bin_sort(N, tile_w, tile_h, n_isects, n_isects, flatten_ids, offsets, workspace, workspace_bytes, stream);
+}
+
+int gspl::bin_lists_known(int N, int mode, const float* means2d, const int32_t* radii, const float* conics, const float* opacities,
+                          const int32_t* order, const int64_t* cum_tiles, const int32_t* big_list, const void* spans,
+                          int tile_size, int tile_w, int tile_h, int64_t n_isects, gspl_alloc_fn alloc, void* alloc_ctx,
+                          int32_t** flatten_ids, int32_t* offsets, void* stream, const char* who) {
+    *flatten_ids = nullptr;
+    if (n_isects > (int64_t)((1u << 30) - 1u)) {
+        set_error(who, "more than 2^30-1 (tile, Gaussian) intersections in one frame: the per-tile lists hold at most 1073741823 entries");
+        return GSPL_ERR_UNSUPPORTED;
+    }
+    if (N <= 0 || n_isects <= 0) return gspl_bin_sort(0, tile_w, tile_h, 0, 0, nullptr, offsets, nullptr, 0, stream);      // (zeros)
+    const size_t ws_bytes = gspl_bin_workspace_bytes(N, n_isects);
+    auto no_block = [&]() { set_error(who, "allocation call-back returned NULL: invalid argument"); return GSPL_ERR_INVALID_ARG; };
+    void* ws = alloc(alloc_ctx, GSPL_BUF_LISTS_WORK, ws_bytes);
+    if (!ws) return no_block();
+    const int rc = gspl_bin_emit(N, mode, means2d, radii, conics, opacities, order, cum_tiles, big_list, spans, tile_size, tile_w, tile_h, n_isects,
+                                 ws, ws_bytes, stream);
+    if (rc != GSPL_OK) return rc;
+    *flatten_ids = (int32_t*)alloc(alloc_ctx, GSPL_BUF_LISTS, 4 * (size_t)n_isects);
+    if (!*flatten_ids) return no_block();
+    return gspl_bin_sort(N, tile_w, tile_h, n_isects, n_isects, *flatten_ids, offsets, ws, ws_bytes, stream);
 }
 
 extern "C" size_t gspl_isect_workspace_bytes(int N, int64_t n_isects) {

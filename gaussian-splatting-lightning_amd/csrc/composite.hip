@@ -353,17 +353,10 @@ int gspl::composite_fwd_impl(int N, int64_t n_isects, int D, int mode, int layou
     const ListTiles lt = list_tiles(tile_size, tile_w, tile_h);
     const int ctw = (width + TILE - 1) / TILE, n_tiles = ctw * ((height + TILE - 1) / TILE);
     hipStream_t s = (hipStream_t)stream;
-    rc = GSPL_ERR_UNSUPPORTED;
-#define CALL_FWD(kD, M, C) rc = launch_fwd<kD, M, C>(n_tiles, ctw, width, height, n_isects, means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids, out_colors, out_alphas, final_Ts, last_ids, hit_flags, s, lt, seg)
-    if (mode == GSPL_MODE_GSPLAT) {
-        if (layout == GSPL_LAYOUT_HWC) { GSPL_DISPATCH_D(D, GSPL_MODE_GSPLAT, false, CALL_FWD) }
-        else { GSPL_DISPATCH_D(D, GSPL_MODE_GSPLAT, true, CALL_FWD) }
-    } else {
-        if (layout == GSPL_LAYOUT_HWC) { GSPL_DISPATCH_D(D, GSPL_MODE_INRIA, false, CALL_FWD) }
-        else { GSPL_DISPATCH_D(D, GSPL_MODE_INRIA, true, CALL_FWD) }
-    }
-#undef CALL_FWD
-    return rc;
+    return dispatch_composite(D, mode, layout, [&](auto d, auto m, auto chw) {
+        return launch_fwd<d(), m(), chw()>(n_tiles, ctw, width, height, n_isects, means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids,
+                                           out_colors, out_alphas, final_Ts, last_ids, hit_flags, s, lt, seg);
+    });
 }
 
 extern "C" int gspl_composite_scores(int N, int64_t n_isects, int mode,

@@ -599,17 +599,11 @@ extern "C" int gspl_composite_bwd(int N, int64_t n_isects, int D, int mode, int 
     const int ctw = (width + TILE - 1) / TILE, n_tiles = ctw * ((height + TILE - 1) / TILE);      // 16x16 compute tiles
     hipStream_t s = (hipStream_t)stream;
     const bool absgrad = v_means2d_abs != nullptr;
-    rc = GSPL_ERR_UNSUPPORTED;
-#define CALL_BWD(kD, M, C) rc = launch_bwd<kD, M, C>(absgrad, n_tiles, ctw, width, height, n_isects, means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids, final_Ts, last_ids, v_out_colors, v_out_alphas, v_means2d, v_means2d_abs, v_conics, v_colors, v_opacities, s, 0, hit_flags, lt)
-    if (mode == GSPL_MODE_GSPLAT) {
-        if (layout == GSPL_LAYOUT_HWC) { GSPL_DISPATCH_D(D, GSPL_MODE_GSPLAT, false, CALL_BWD) }
-        else { GSPL_DISPATCH_D(D, GSPL_MODE_GSPLAT, true, CALL_BWD) }
-    } else {
-        if (layout == GSPL_LAYOUT_HWC) { GSPL_DISPATCH_D(D, GSPL_MODE_INRIA, false, CALL_BWD) }
-        else { GSPL_DISPATCH_D(D, GSPL_MODE_INRIA, true, CALL_BWD) }
-    }
-#undef CALL_BWD
-    return rc;
+    return dispatch_composite(D, mode, layout, [&](auto d, auto m, auto chw) {
+        return launch_bwd<d(), m(), chw()>(absgrad, n_tiles, ctw, width, height, n_isects, means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids,
+                                           final_Ts, last_ids, v_out_colors, v_out_alphas, v_means2d, v_means2d_abs, v_conics, v_colors, v_opacities, s, 0,
+                                           hit_flags, lt);
+    });
 }
 
 // ---- deterministic (debug) mode ----------------------------------------------------------------------------------------------
@@ -618,7 +612,8 @@ extern "C" int gspl_composite_bwd(int N, int64_t n_isects, int D, int mode, int 
 // its tiles: run-to-run differences of 1e-7 relative, which tests of HIP against HIP could only bound (1e-4 after the projection
 // chain, profiles/r04_flaky_v_means.txt).  In this mode the kernel writes one row per list entry (single writer), the entries
 // are sorted by splat id (stable: ties in list order) and one thread per splat adds its rows in that order.  Three extra passes over
-// the entries and scratch from hipMallocAsync: a mode for tests and debugging, not for the timed path.
+// the entries and one block of scratch (here from hipMallocAsync; the surfel backward, which runs the same reduction, asks its
+// call-back): a mode for tests and debugging, not for the timed path.
 #include "gspl_sort.h"
 namespace gspl {
 static int g_deterministic = 0;
@@ -628,24 +623,51 @@ __global__ __launch_bounds__(256) void iota_ids_kernel(int64_t n, const int32_t*
     if (i < n) { keys[i] = (uint32_t)ids[i]; pos[i] = (uint32_t)i; }
 }
 // thread i = the first entry of a run of equal ids (sorted, stable): adds the run's rows in list order into the splat's row
+static constexpr int ORDERED_MAX_NV = 18;      // the surfel backward's row; compositing: 6 + D + 2 <= 16
 __global__ __launch_bounds__(256) void ordered_reduce_kernel(int64_t n, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ pos,
-                                                             const float* __restrict__ entries, int nv, int entry_stride,
-                                                             float* __restrict__ v_packed, int packed_stride) {
+                                                             const float* __restrict__ entries, int nv, float* __restrict__ rows, int row_stride) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const uint32_t g = keys[i];
     if (i > 0 && keys[i - 1] == g) return;
-    float acc[16];
+    float acc[ORDERED_MAX_NV];
 #pragma unroll
-    for (int k = 0; k < 16; ++k) acc[k] = 0.f;
+    for (int k = 0; k < ORDERED_MAX_NV; ++k) acc[k] = 0.f;
     for (int64_t j = i; j < n && keys[j] == g; ++j) {
-        const float* row = entries + (int64_t)pos[j] * entry_stride;
+        const float* row = entries + (int64_t)pos[j] * nv;
 #pragma unroll
-        for (int k = 0; k < 16; ++k) if (k < nv) acc[k] += row[k];
+        for (int k = 0; k < ORDERED_MAX_NV; ++k) if (k < nv) acc[k] += row[k];
     }
-    float* out = v_packed + (int64_t)g * packed_stride;
+    float* out = rows + (int64_t)g * row_stride;
 #pragma unroll
-    for (int k = 0; k < 16; ++k) if (k < nv) out[k] += acc[k];      // (the row was zero, or holds what the caller put there: one writer)
+    for (int k = 0; k < ORDERED_MAX_NV; ++k) if (k < nv) out[k] += acc[k];      // (the row was zero, or holds what the caller put there: one writer)
+}
+
+OrderedScratch ordered_scratch(int N, int64_t n_isects, int nv) {
+    OrderedScratch o;
+    o.id_bits = 1;
+    while (o.id_bits < 32 && (1ll << o.id_bits) < (long long)N) ++o.id_bits;
+    o.sort_ws_bytes = gspl_radix_sort_workspace_bytes(n_isects, 4, 0, o.id_bits);
+    Carve c;
+    (void)c.take((size_t)n_isects * nv * sizeof(float));      // the entries' rows: the block starts with them
+    o.keys = c.take((size_t)n_isects * 4 * sizeof(uint32_t));
+    o.sort_ws = c.take(o.sort_ws_bytes ? o.sort_ws_bytes : 16);
+    o.total = c.off;
+    return o;
+}
+
+int ordered_reduce(int N, int64_t n_isects, int nv, const int32_t* flatten_ids, void* block, float* rows, int row_stride, hipStream_t s, const char* who) {
+    if (nv > ORDERED_MAX_NV) return fail_arg(who);
+    const OrderedScratch o = ordered_scratch(N, n_isects, nv);
+    uint32_t *k0 = (uint32_t*)((char*)block + o.keys), *k1 = k0 + n_isects, *p0 = k1 + n_isects, *p1 = p0 + n_isects;
+    const unsigned grid = (unsigned)((n_isects + 255) / 256);
+    hipLaunchKernelGGL(iota_ids_kernel, dim3(grid), dim3(256), 0, s, n_isects, flatten_ids, k0, p0);
+    int which = 0;
+    const int rc = gspl_radix_sort_pairs_u32(n_isects, k0, k1, p0, p1, 0, o.id_bits, &which, (char*)block + o.sort_ws, o.sort_ws_bytes, s);
+    if (rc != GSPL_OK) return rc;
+    hipLaunchKernelGGL(ordered_reduce_kernel, dim3(grid), dim3(256), 0, s, n_isects, which ? k1 : k0, which ? p1 : p0,
+                       (const float*)block, nv, rows, row_stride);
+    return check_launch(who);
 }
 }  // namespace gspl
 
@@ -693,48 +715,25 @@ int gspl::composite_bwd_packed_impl(int N, int64_t n_isects, int D, int mode, in
     const int nv = 6 + D + (ag ? 2 : 0);
     const bool ordered = gspl_get_deterministic() != 0 && lt.log2 == 4 && n_isects > 0;
     float* entries = nullptr;
-    uint32_t *k0 = nullptr, *k1 = nullptr, *p0 = nullptr, *p1 = nullptr;
-    void* sort_ws = nullptr;
-    size_t sort_ws_bytes = 0;
-    int id_bits = 1;
     float* const v_packed_out = v_packed;
     const int packed_stride_out = packed_stride;
     if (ordered) {
         if (n_isects < 0) return fail_arg("composite_bwd_packed: the deterministic mode needs the list length on the host (n_isects >= 0)");
-        while (id_bits < 32 && (1ll << id_bits) < (long long)N) ++id_bits;
-        sort_ws_bytes = gspl_radix_sort_workspace_bytes(n_isects, 4, 0, id_bits);
-        hipError_t e = hipMallocAsync((void**)&entries, (size_t)n_isects * nv * sizeof(float), s);
-        if (e == hipSuccess) e = hipMallocAsync((void**)&k0, (size_t)n_isects * 4 * sizeof(uint32_t), s);
-        if (e == hipSuccess) e = hipMallocAsync(&sort_ws, sort_ws_bytes ? sort_ws_bytes : 16, s);
+        hipError_t e = hipMallocAsync((void**)&entries, ordered_scratch(N, n_isects, nv).total, s);
         if (e == hipSuccess) e = hipMemsetAsync(entries, 0, (size_t)n_isects * nv * sizeof(float), s);
         if (e != hipSuccess) return check_hip(e, "composite_bwd_packed(deterministic): scratch");
-        k1 = k0 + n_isects; p0 = k1 + n_isects; p1 = p0 + n_isects;
         v_packed = entries;
         packed_stride = -nv;
+        seg = nullptr;      // (rows per list entry, one writer each: the plain walk)
     }
-    rc = GSPL_ERR_UNSUPPORTED;
-    if (ordered) seg = nullptr;      // (rows per list entry, one writer each: the plain walk)
-#define CALL_BWDP(kD, M, C) rc = launch_bwd<kD, M, C, true>(ag, n_tiles, ctw, width, height, n_isects, means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids, final_Ts, last_ids, v_out_colors, v_out_alphas, v_packed, nullptr, nullptr, nullptr, nullptr, s, packed_stride, hit_flags, lt, seg)
-    if (mode == GSPL_MODE_GSPLAT) {
-        if (layout == GSPL_LAYOUT_HWC) { GSPL_DISPATCH_D(D, GSPL_MODE_GSPLAT, false, CALL_BWDP) }
-        else { GSPL_DISPATCH_D(D, GSPL_MODE_GSPLAT, true, CALL_BWDP) }
-    } else {
-        if (layout == GSPL_LAYOUT_HWC) { GSPL_DISPATCH_D(D, GSPL_MODE_INRIA, false, CALL_BWDP) }
-        else { GSPL_DISPATCH_D(D, GSPL_MODE_INRIA, true, CALL_BWDP) }
-    }
-#undef CALL_BWDP
+    rc = dispatch_composite(D, mode, layout, [&](auto d, auto m, auto chw) {
+        return launch_bwd<d(), m(), chw(), true>(ag, n_tiles, ctw, width, height, n_isects, means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids,
+                                                 final_Ts, last_ids, v_out_colors, v_out_alphas, v_packed, nullptr, nullptr, nullptr, nullptr, s, packed_stride,
+                                                 hit_flags, lt, seg);
+    });
     if (ordered) {
-        if (rc == GSPL_OK) {
-            hipLaunchKernelGGL(iota_ids_kernel, dim3((unsigned)((n_isects + 255) / 256)), dim3(256), 0, s, n_isects, flatten_ids, k0, p0);
-            int which = 0;
-            rc = gspl_radix_sort_pairs_u32(n_isects, k0, k1, p0, p1, 0, id_bits, &which, sort_ws, sort_ws_bytes, s);
-            if (rc == GSPL_OK) {
-                hipLaunchKernelGGL(ordered_reduce_kernel, dim3((unsigned)((n_isects + 255) / 256)), dim3(256), 0, s, n_isects, which ? k1 : k0, which ? p1 : p0,
-                                   entries, nv, nv, v_packed_out, packed_stride_out);
-                rc = check_launch("composite_bwd_packed(ordered reduce)");
-            }
-        }
-        (void)hipFreeAsync(entries, s); (void)hipFreeAsync(k0, s); (void)hipFreeAsync(sort_ws, s);
+        if (rc == GSPL_OK) rc = ordered_reduce(N, n_isects, nv, flatten_ids, entries, v_packed_out, packed_stride_out, s, "composite_bwd_packed(ordered reduce)");
+        (void)hipFreeAsync(entries, s);
     }
     return rc;
 }

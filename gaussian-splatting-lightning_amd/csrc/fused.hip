@@ -399,33 +399,20 @@ extern "C" int gspl_rasterize_inria_fwd(
                 if (rc != GSPL_OK) return rc;
                 if (!arrived) return check_hip(hipStreamSynchronize(s), "rasterize_inria_fwd: the list length never arrived") ? GSPL_ERR_LAUNCH : fail_arg("rasterize_inria_fwd: the list length never arrived");
                 if (n_isects <= capacity) { st->n_isects = n_isects; return GSPL_OK; }
-                ws2 = nullptr;                                  // too low a guess: the frame is redone below with the real length
+                // too low a guess: the frame's lists are redone below with the real length
             } else {
                 if (!wait_count()) return check_hip(hipStreamSynchronize(s), "rasterize_inria_fwd: the list length never arrived") ? GSPL_ERR_LAUNCH : fail_arg("rasterize_inria_fwd: the list length never arrived");
                 n_isects = host[0];
             }
-            if (n_isects > (int64_t)((1u << 30) - 1u)) {
-                set_error("rasterize_inria_fwd", "more than 2^30-1 (tile, Gaussian) intersections in one frame: the per-tile lists hold at most 1073741823 entries");
-                return GSPL_ERR_UNSUPPORTED;
-            }
-            if (n_isects > 0 && (!ws2 || capacity < n_isects)) {
-                capacity = n_isects;
-                ws2_bytes = gspl_bin_workspace_bytes(N, capacity);
-                ws2 = (char*)alloc(alloc_ctx, GSPL_BUF_LISTS_WORK, ws2_bytes);
-                if (!ws2) return fail_arg("rasterize_inria_fwd: allocation call-back returned NULL");
-                rc = gspl_bin_emit(N, GSPL_MODE_INRIA, st->means2d, radii, st->conics, opacities, order, cum, big_list, spans, tile, tile_w, tile_h,
-                                   capacity, ws2, ws2_bytes, s);
-                if (rc != GSPL_OK) return rc;
-            }
-            st->flatten_ids = n_isects > 0 ? (int32_t*)alloc(alloc_ctx, GSPL_BUF_LISTS, 4 * (size_t)n_isects) : nullptr;
-            if (n_isects > 0 && !st->flatten_ids) return fail_arg("rasterize_inria_fwd: allocation call-back returned NULL");
-            if (n_isects > 0) (void)make_seg(n_isects); else (void)make_seg(0);
-            rc = gspl_bin_sort(N, tile_w, tile_h, n_isects, capacity > n_isects ? capacity : n_isects, st->flatten_ids, st->offsets, ws2, ws2_bytes, s);
+            rc = bin_lists_known(N, GSPL_MODE_INRIA, st->means2d, radii, st->conics, opacities, order, cum, big_list, spans, tile, tile_w, tile_h, n_isects,
+                                 alloc, alloc_ctx, &st->flatten_ids, st->offsets, s, "rasterize_inria_fwd");
             if (rc != GSPL_OK) return rc;
+            (void)make_seg(n_isects);      // (the checkpoint block: only the compositing launch needs it)
         }
         if (ev_col) (void)hipStreamWaitEvent(s, ev_col, 0);      // colours are ready before compositing reads them
     } else {
-        rc = gspl_bin_sort(0, tile_w, tile_h, 0, 0, nullptr, st->offsets, nullptr, 0, s);
+        rc = bin_lists_known(0, GSPL_MODE_INRIA, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tile, tile_w, tile_h, 0,
+                             alloc, alloc_ctx, &st->flatten_ids, st->offsets, s, "rasterize_inria_fwd");
         if (rc != GSPL_OK) return rc;
     }
     st->n_isects = n_isects;

@@ -222,13 +222,30 @@ int composite_bwd_packed_impl(int N, int64_t n_isects, int D, int mode, int layo
                               const float* v_out_colors, const float* v_out_alphas, float* v_packed, int packed_stride, int absgrad, uint8_t* hit_flags,
                               void* stream, const SegState* seg);
 
-}  // namespace gspl
+// One launch of a kernel family templated on <D, MODE, CHW>: f(D, MODE, CHW) gets the three as std::integral_constants and returns the
+// call's code.  check_composite_args has refused every other mode and layout; a D outside {1, 2, 3, 4, 8} is GSPL_ERR_UNSUPPORTED.
+template <class F>
+static int dispatch_composite(int D, int mode, int layout, F&& f) {
+    auto with_d = [&](auto mode_c, auto chw_c) -> int {
+        switch (D) {
+            case 1: return f(std::integral_constant<int, 1>{}, mode_c, chw_c);
+            case 2: return f(std::integral_constant<int, 2>{}, mode_c, chw_c);
+            case 3: return f(std::integral_constant<int, 3>{}, mode_c, chw_c);
+            case 4: return f(std::integral_constant<int, 4>{}, mode_c, chw_c);
+            case 8: return f(std::integral_constant<int, 8>{}, mode_c, chw_c);
+        }
+        return GSPL_ERR_UNSUPPORTED;
+    };
+    return dispatch_bools([&](auto inria, auto chw) { return with_d(std::integral_constant<int, decltype(inria)::value ? GSPL_MODE_INRIA : GSPL_MODE_GSPLAT>{}, chw); },
+                          mode != GSPL_MODE_GSPLAT, layout != GSPL_LAYOUT_HWC);
+}
 
-#define GSPL_DISPATCH_D(D_, MODE_, CHW_, CALL)                    \
-    switch (D_) {                                                 \
-        case 1: { constexpr int kD = 1; CALL(kD, MODE_, CHW_); } break; \
-        case 2: { constexpr int kD = 2; CALL(kD, MODE_, CHW_); } break; \
-        case 3: { constexpr int kD = 3; CALL(kD, MODE_, CHW_); } break; \
-        case 4: { constexpr int kD = 4; CALL(kD, MODE_, CHW_); } break; \
-        case 8: { constexpr int kD = 8; CALL(kD, MODE_, CHW_); } break; \
-    }
+// The deterministic mode's ordered reduction (composite_bwd.hip; gspl_set_deterministic): a backward that wrote one row of `nv` (<= 18)
+// floats per list entry adds, per splat, its entries' rows IN LIST ORDER into rows[splat * row_stride ...] (which the caller cleared,
+// or filled with what the sums are added to).  One block of ordered_scratch(...).total bytes, carved as entries | four key arrays | the
+// sort's workspace: it starts with the entries' rows, which the caller clears before the backward that fills them.
+struct OrderedScratch { size_t keys, sort_ws, sort_ws_bytes, total; int id_bits; };
+OrderedScratch ordered_scratch(int N, int64_t n_isects, int nv);
+int ordered_reduce(int N, int64_t n_isects, int nv, const int32_t* flatten_ids, void* block, float* rows, int row_stride, hipStream_t s, const char* who);
+
+}  // namespace gspl

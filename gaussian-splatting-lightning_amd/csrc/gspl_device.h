@@ -32,6 +32,25 @@ template <> struct ModeTraits<GSPL_MODE_INRIA> {
 static constexpr float kAlphaMin = 1.0f / 255.0f;
 static constexpr float kTStop = 1e-4f;
 
+// ---- tile rectangle of one splat, per API convention
+template <int MODE>
+__device__ __forceinline__ void tile_rect(float x, float y, int radius, int tile_size, int tile_w, int tile_h,
+                                          int& minx, int& miny, int& maxx, int& maxy) {
+    const float ts = (float)tile_size;
+    const float r = (float)radius;
+    if (MODE == GSPL_MODE_GSPLAT) {
+        // gaussian_projection.py:117-125 : trunc((p - r)/T), trunc((p + r)/T) + 1
+        minx = (int)((x - r) / ts); miny = (int)((y - r) / ts);
+        maxx = (int)((x + r) / ts) + 1; maxy = (int)((y + r) / ts) + 1;
+    } else {
+        // Inria getRect: (int)((p - r)/T), (int)((p + r + T - 1)/T)
+        minx = (int)((x - r) / ts); miny = (int)((y - r) / ts);
+        maxx = (int)((x + r + ts - 1.f) / ts); maxy = (int)((y + r + ts - 1.f) / ts);
+    }
+    minx = min(max(minx, 0), tile_w); maxx = min(max(maxx, 0), tile_w);
+    miny = min(max(miny, 0), tile_h); maxy = min(max(maxy, 0), tile_h);
+}
+
 // ---- rotation from quaternion (w,x,y,z), used as given (gaussian_projection.py:211-232) --------
 __device__ __forceinline__ void quat_to_rotmat(const float q[4], float R[9]) {
     const float w = q[0], x = q[1], y = q[2], z = q[3];

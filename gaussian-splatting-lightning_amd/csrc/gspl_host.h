@@ -1,6 +1,7 @@
 // gspl_host.h — host-side helpers shared by the C-ABI translation units.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "../../include/gspl_hip.h"
 
 namespace gspl {
@@ -39,6 +40,15 @@ struct Carve {
     size_t off = 0;
     size_t take(size_t bytes) { const size_t o = off; off = up256(off + bytes); return o; }
 };
+
+// Run-time flags as template arguments: f is called with one std::bool_constant per flag, in the flags' order, and its result returned.
+template <class F>
+auto dispatch_bools(F&& f) { return f(); }
+template <class F, class... Bs>
+auto dispatch_bools(F&& f, bool b, Bs... rest) {
+    auto bound = [&](auto c) { return dispatch_bools([&](auto... cs) { return f(c, cs...); }, rest...); };
+    return b ? bound(std::true_type{}) : bound(std::false_type{});
+}
 
 // The pinned host words a binning scan stores the frame's list length into: one block of four per host thread, kept for the process.
 // The calls that use it read their words before they return.  NULL (HIP's error cleared) when it cannot be allocated.
@@ -85,6 +95,13 @@ int bin_emit_impl(int N, int mode, const float* means2d, const int32_t* radii, c
                   const int32_t* order, const int64_t* cum_tiles, const int32_t* big_list, const void* spans,
                   int tile_size, int tile_w, int tile_h, int64_t capacity, void* workspace, size_t workspace_bytes, void* stream,
                   bool tile_header_zeroed);
+// The tile lists of a frame whose list length the host has read (count done, nothing emitted, or emitted into too little room): refuses
+// more than 2^30-1 entries, then asks `alloc` for GSPL_BUF_LISTS_WORK, emits, asks for GSPL_BUF_LISTS and sorts, in that order.  No
+// entries: *flatten_ids = NULL and `offsets` is filled with zeros.  `who` names the caller in the error texts.
+int bin_lists_known(int N, int mode, const float* means2d, const int32_t* radii, const float* conics, const float* opacities,
+                    const int32_t* order, const int64_t* cum_tiles, const int32_t* big_list, const void* spans,
+                    int tile_size, int tile_w, int tile_h, int64_t n_isects, gspl_alloc_fn alloc, void* alloc_ctx,
+                    int32_t** flatten_ids, int32_t* offsets, void* stream, const char* who);
 // the density controller's statistics (gspl_densify_stats) applied by the preprocess backward itself; accum == NULL: not asked for
 struct BwdStats { float* accum = nullptr; float* denom = nullptr; float* max_radii = nullptr; };
 // inria.hip -> fused.hip: the geometry phase and the preprocess backward with the model's RAW parameters (GSPL_INRIA_RAW_PARAMS)
@@ -92,9 +109,9 @@ int inria_geometry_launch(int N, const float* means, const float* scales, const 
                           const float* viewmatrix, const float* projmatrix, int width, int height, int tile_size,
                           float tanfovx, float tanfovy, float scale_modifier,
                           int32_t* radii, float* means2d, float* depths, float* conics, float* cov3d,
-                          const float* raw_opacities /* nullable: activated parameters */, float* opacities_out, hipStream_t s,
-                          ZeroJob zero = ZeroJob() /* cleared by the same kernel, for the binning that follows */,
-                          int ext = 0 /* GSPL_INRIA_ANTIALIAS (+ GSPL_INRIA_RAW_PARAMS): raw_opacities = the caller's opacities, raw or not */);
+                          const float* raw_opacities /* the caller's opacities, raw or not; read with either bit of `ext` */, float* opacities_out,
+                          hipStream_t s, ZeroJob zero = ZeroJob() /* cleared by the same kernel, for the binning that follows */,
+                          int ext = 0 /* GSPL_INRIA_RAW_PARAMS and / or GSPL_INRIA_ANTIALIAS: the one place that says RAW */);
 // [N,4] rows colour | 1 / z for the inverse-depth channel of the fused call (GSPL_INRIA_INVDEPTH); colors4 16-byte aligned
 int inria_invdepth_rows_launch(int N, const int32_t* radii, const float* colors3, const float* depths, float* colors4, hipStream_t s);
 int inria_preprocess_bwd_impl(int N, int degree, int n_coeffs, const float* means, const float* scales, const float* quats,
@@ -106,9 +123,9 @@ int inria_preprocess_bwd_impl(int N, int degree, int n_coeffs, const float* mean
                               float* v_means, float* v_scales, float* v_quats,
                               float* v_cov3d_precomp, float* v_shs, float* v_shs_rest, float* v_colors_precomp,
                               float* v_means2d_ndc, const float* v_opacities_packed, float* v_opacities, const float* sh_jac,
-                              const float* opac_act /* nullable: activated parameters */, void* stream,
+                              const float* opac_act /* read with RAW (the activated opacities) or ANTIALIAS (the caller's) in `ext` */, void* stream,
                               const gspl_bwd_adam_plan* adam = nullptr /* not NULL: v_shs / v_shs_rest / v_scales / v_quats / v_opacities are
                               the PARAMETERS (as means, scales, quats are), updated in place; v_means is scratch [N,3] */,
                               BwdStats stats = BwdStats(),
-                              int ext = 0 /* GSPL_INRIA_ANTIALIAS / GSPL_INRIA_INVDEPTH (+ GSPL_INRIA_RAW_PARAMS): see inria.hip */);
+                              int ext = 0 /* GSPL_INRIA_RAW_PARAMS / GSPL_INRIA_ANTIALIAS / GSPL_INRIA_INVDEPTH: see inria.hip */);
 }  // namespace gspl

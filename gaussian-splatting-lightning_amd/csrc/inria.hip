@@ -187,12 +187,9 @@ __global__ __launch_bounds__(256) void inria_preprocess_fwd_kernel(
             const float pw = 1.f / (G.hom[3] + 1e-7f);
             const float x2d = ((G.hom[0] * pw + 1.f) * (float)width - 1.f) * 0.5f;
             const float y2d = ((G.hom[1] * pw + 1.f) * (float)height - 1.f) * 0.5f;
-            const int grid_x = (width + tile_size - 1) / tile_size, grid_y = (height + tile_size - 1) / tile_size;
-            const float ts = (float)tile_size, rf = (float)radius;
-            const int minx = min(grid_x, max(0, (int)((x2d - rf) / ts)));
-            const int miny = min(grid_y, max(0, (int)((y2d - rf) / ts)));
-            const int maxx = min(grid_x, max(0, (int)((x2d + rf + ts - 1.f) / ts)));
-            const int maxy = min(grid_y, max(0, (int)((y2d + rf + ts - 1.f) / ts)));
+            int minx, miny, maxx, maxy;
+            tile_rect<GSPL_MODE_INRIA>(x2d, y2d, radius, tile_size, (width + tile_size - 1) / tile_size, (height + tile_size - 1) / tile_size,
+                                       minx, miny, maxx, maxy);
             if ((maxx - minx) * (maxy - miny) > 0) {
                 o_radius = radius;
                 o_xy[0] = x2d; o_xy[1] = y2d;
@@ -439,30 +436,23 @@ int inria_invdepth_rows_launch(int N, const int32_t* radii, const float* colors3
     return check_launch("inria_invdepth_rows");
 }
 
-// geometry phase, activated parameters (raw_opacities == NULL) or the model's raw ones (-> opacities_out [N] = sigmoid)
+// geometry phase.  ext: GSPL_INRIA_RAW_PARAMS (the model's raw parameters; opacities_out [N] = sigmoid(raw_opacities)) and / or
+// GSPL_INRIA_ANTIALIAS (opacities_out = the effective opacities); with neither, the two opacity pointers are not looked at
 int inria_geometry_launch(int N, const float* means, const float* scales, const float* quats, const float* cov3d_precomp,
                           const float* viewmatrix, const float* projmatrix, int width, int height, int tile_size,
                           float tanfovx, float tanfovy, float scale_modifier,
                           int32_t* radii, float* means2d, float* depths, float* conics, float* cov3d,
                           const float* raw_opacities, float* opacities_out, hipStream_t s, ZeroJob zero, int ext) {
-    const int grid = (N + 255) / 256;
-#define GSPL_LAUNCH_PRE_FWD(R, AAF, OPIN, OPOUT) hipLaunchKernelGGL((inria_preprocess_fwd_kernel<R, AAF>), dim3(grid), dim3(256), 0, s, \
-        N, means, scales, quats, cov3d_precomp, viewmatrix, projmatrix, width, height, tile_size, \
-        tanfovx, tanfovy, scale_modifier, radii, means2d, depths, conics, cov3d, OPIN, OPOUT, zero.p, zero.n16)
-    const bool raw = (ext & GSPL_INRIA_RAW_PARAMS) != 0 || (!(ext & GSPL_INRIA_ANTIALIAS) && raw_opacities);
-    if (ext & GSPL_INRIA_ANTIALIAS) {
-        // (`raw_opacities`: the caller's opacities, raw with GSPL_INRIA_RAW_PARAMS in `ext`, activated without)
-        if (!raw_opacities || !opacities_out || (raw && cov3d_precomp))
-            return fail_arg("inria_preprocess_fwd(antialias): needs the opacities and room for the effective ones (raw: scales + rotations)");
-        if (raw) GSPL_LAUNCH_PRE_FWD(true, true, raw_opacities, opacities_out);
-        else GSPL_LAUNCH_PRE_FWD(false, true, raw_opacities, opacities_out);
-    } else if (raw_opacities) {
-        if (cov3d_precomp || !opacities_out) return fail_arg("inria_preprocess_fwd: raw parameters need scales + rotations and room for the opacities");
-        GSPL_LAUNCH_PRE_FWD(true, false, raw_opacities, opacities_out);
-    } else {
-        GSPL_LAUNCH_PRE_FWD(false, false, (const float*)nullptr, (float*)nullptr);
-    }
-#undef GSPL_LAUNCH_PRE_FWD
+    const bool raw = (ext & GSPL_INRIA_RAW_PARAMS) != 0, aa = (ext & GSPL_INRIA_ANTIALIAS) != 0;
+    // (`raw_opacities`: the caller's opacities, raw with GSPL_INRIA_RAW_PARAMS in `ext`, activated without)
+    if (aa && (!raw_opacities || !opacities_out || (raw && cov3d_precomp)))
+        return fail_arg("inria_preprocess_fwd(antialias): needs the opacities and room for the effective ones (raw: scales + rotations)");
+    if (raw && (cov3d_precomp || !raw_opacities || !opacities_out)) return fail_arg("inria_preprocess_fwd: raw parameters need scales + rotations and room for the opacities");
+    dispatch_bools([&](auto R, auto AA) {
+        hipLaunchKernelGGL((inria_preprocess_fwd_kernel<R(), AA()>), dim3((N + 255) / 256), dim3(256), 0, s,
+                           N, means, scales, quats, cov3d_precomp, viewmatrix, projmatrix, width, height, tile_size,
+                           tanfovx, tanfovy, scale_modifier, radii, means2d, depths, conics, cov3d, raw_opacities, opacities_out, zero.p, zero.n16);
+    }, raw, aa);
     return check_launch("inria_preprocess_fwd");
 }
 
@@ -508,7 +498,8 @@ extern "C" int gspl_inria_preprocess_fwd(int N, int degree, int n_coeffs,
 }
 
 namespace gspl {
-// opac_act != NULL: scales / quats are RAW parameters (see inria_preprocess_fwd_kernel<true>), opac_act the activated opacities
+// GSPL_INRIA_RAW_PARAMS in `ext`: scales / quats are RAW parameters (see inria_preprocess_fwd_kernel<true>) and opac_act the activated
+// opacities (with GSPL_INRIA_ANTIALIAS: the caller's opacities, raw or not)
 int inria_preprocess_bwd_impl(int N, int degree, int n_coeffs,
                                          const float* means, const float* scales, const float* quats,
                                          const float* cov3d, const float* shs, const float* shs_rest,
@@ -521,8 +512,7 @@ int inria_preprocess_bwd_impl(int N, int degree, int n_coeffs,
                                          float* v_means2d_ndc, const float* v_opacities_packed, float* v_opacities, const float* sh_jac,
                                          const float* opac_act, void* stream, const gspl_bwd_adam_plan* plan, BwdStats stats, int ext) {
     if (N < 0 || width <= 0 || height <= 0) return fail_arg("inria_preprocess_bwd: bad sizes");
-    // ext: the fused call's GSPL_INRIA_ANTIALIAS / GSPL_INRIA_INVDEPTH bits, and GSPL_INRIA_RAW_PARAMS beside ANTIALIAS (whose `opac_act` is
-    // the caller's opacities, raw or not; without it a non-NULL `opac_act` says RAW, as before)
+    // ext: the fused call's GSPL_INRIA_RAW_PARAMS / GSPL_INRIA_ANTIALIAS / GSPL_INRIA_INVDEPTH bits
     if (ext & ~(GSPL_INRIA_RAW_PARAMS | GSPL_INRIA_ANTIALIAS | GSPL_INRIA_INVDEPTH)) return fail_arg("inria_preprocess_bwd: unknown extension bits");
     if ((ext & (GSPL_INRIA_ANTIALIAS | GSPL_INRIA_INVDEPTH)) && plan) return fail_arg("inria_preprocess_bwd(adam): neither anti-aliasing nor inverse depth is supported with the optimizer inside the backward");
     if ((ext & GSPL_INRIA_ANTIALIAS) && (!opac_act || !v_opacities)) return fail_arg("inria_preprocess_bwd(antialias): needs the opacities and v_opacities");
@@ -577,8 +567,8 @@ int inria_preprocess_bwd_impl(int N, int degree, int n_coeffs,
         if (rc != GSPL_OK) return rc;
     }
     const bool aa = (ext & GSPL_INRIA_ANTIALIAS) != 0, invd = (ext & GSPL_INRIA_INVDEPTH) != 0;
-    const bool raw = aa ? (ext & GSPL_INRIA_RAW_PARAMS) != 0 : opac_act != nullptr;
-    if (raw && (!v_scales || !v_opacities || v_cov3d_precomp)) return fail_arg("inria_preprocess_bwd: raw parameters need v_scales, v_quats and v_opacities");
+    const bool raw = (ext & GSPL_INRIA_RAW_PARAMS) != 0;
+    if (raw && (!opac_act || !v_scales || !v_opacities || v_cov3d_precomp)) return fail_arg("inria_preprocess_bwd: raw parameters need v_scales, v_quats and v_opacities");
     PreAdam pre = {};
     if (plan) {
         auto target = [](float* p, const gspl_bwd_adam_tensor& t) {
@@ -589,23 +579,14 @@ int inria_preprocess_bwd_impl(int N, int degree, int n_coeffs,
         pre.quats = target(v_quats, plan->rotations);
         pre.opac = target(v_opacities, plan->opacities);
     }
-#define GSPL_PRE_BWD_ARGS N, means, scales, quats, cov3d, viewmatrix, projmatrix, width, height, tanfovx, tanfovy, scale_modifier, \
-        radii, v_means2d, v_conics, gs2, gs3, v_means, v_scales, v_quats, v_cov3d_precomp, v_means2d_ndc, v_opacities_packed, v_opacities, opac_act, pre, stats
-#define GSPL_LAUNCH_PRE_BWD(A, R, AD) hipLaunchKernelGGL((inria_preprocess_bwd_kernel<A, R, AD>), dim3(grid), dim3(256), 0, s, GSPL_PRE_BWD_ARGS)
-#define GSPL_LAUNCH_PRE_BWD_EXT(A, R, AAF, INVDF) hipLaunchKernelGGL((inria_preprocess_bwd_kernel<A, R, false, AAF, INVDF>), dim3(grid), dim3(256), 0, s, GSPL_PRE_BWD_ARGS)
-#define GSPL_LAUNCH_PRE_BWD_EXT4(AAF, INVDF) do { \
-        if (accum) { if (raw) GSPL_LAUNCH_PRE_BWD_EXT(true, true, AAF, INVDF); else GSPL_LAUNCH_PRE_BWD_EXT(true, false, AAF, INVDF); } \
-        else { if (raw) GSPL_LAUNCH_PRE_BWD_EXT(false, true, AAF, INVDF); else GSPL_LAUNCH_PRE_BWD_EXT(false, false, AAF, INVDF); } } while (0)
-    if (aa && invd) GSPL_LAUNCH_PRE_BWD_EXT4(true, true);
-    else if (aa) GSPL_LAUNCH_PRE_BWD_EXT4(true, false);
-    else if (invd) GSPL_LAUNCH_PRE_BWD_EXT4(false, true);
-    else if (plan) { if (opac_act) GSPL_LAUNCH_PRE_BWD(true, true, true); else GSPL_LAUNCH_PRE_BWD(true, false, true); }
-    else if (accum) { if (opac_act) GSPL_LAUNCH_PRE_BWD(true, true, false); else GSPL_LAUNCH_PRE_BWD(true, false, false); }
-    else { if (opac_act) GSPL_LAUNCH_PRE_BWD(false, true, false); else GSPL_LAUNCH_PRE_BWD(false, false, false); }
-#undef GSPL_LAUNCH_PRE_BWD_EXT4
-#undef GSPL_LAUNCH_PRE_BWD_EXT
-#undef GSPL_LAUNCH_PRE_BWD
-#undef GSPL_PRE_BWD_ARGS
+    // ADAM goes with neither AA nor INVD (refused above) and always accumulates (it needs v_shs): the other combinations do not exist
+    dispatch_bools([&](auto A, auto R, auto AD, auto AAF, auto INVDF) {
+        if constexpr (!AD() || (A() && !AAF() && !INVDF()))
+            hipLaunchKernelGGL((inria_preprocess_bwd_kernel<A(), R(), AD(), AAF(), INVDF()>), dim3(grid), dim3(256), 0, s,
+                               N, means, scales, quats, cov3d, viewmatrix, projmatrix, width, height, tanfovx, tanfovy, scale_modifier,
+                               radii, v_means2d, v_conics, gs2, gs3, v_means, v_scales, v_quats, v_cov3d_precomp, v_means2d_ndc, v_opacities_packed,
+                               v_opacities, opac_act, pre, stats);
+    }, accum, raw, plan != nullptr, aa, invd);
     return check_launch("inria_preprocess_bwd");
 }
 }  // namespace gspl

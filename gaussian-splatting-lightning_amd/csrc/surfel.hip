@@ -26,7 +26,6 @@
 // through one function and must take the same skip / stop decisions.
 #pragma clang fp contract(on)
 #include "gspl_composite.h"
-#include "gspl_sort.h"
 #include <cstring>
 
 namespace gspl {
@@ -380,30 +379,6 @@ __global__ __launch_bounds__(256) void surfel_bwd_kernel(
     }
 }
 
-// deterministic mode: thread i = the first entry of a run of equal splat ids (sorted, stable): adds the run's rows in list order
-__global__ __launch_bounds__(256) void surfel_ordered_reduce_kernel(int64_t n, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ pos,
-                                                                    const float* __restrict__ entries, float* __restrict__ v_rows) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t g = keys[i];
-    if (i > 0 && keys[i - 1] == g) return;
-    float acc[SURF_GRAD];
-#pragma unroll
-    for (int k = 0; k < SURF_GRAD; ++k) acc[k] = 0.f;
-    for (int64_t j = i; j < n && keys[j] == g; ++j) {
-        const float* row = entries + (int64_t)pos[j] * SURF_GRAD;
-#pragma unroll
-        for (int k = 0; k < SURF_GRAD; ++k) acc[k] += row[k];
-    }
-#pragma unroll
-    for (int k = 0; k < SURF_GRAD; ++k) v_rows[(int64_t)g * SURF_GRAD + k] = acc[k];
-}
-
-__global__ __launch_bounds__(256) void surfel_iota_kernel(int64_t n, const int32_t* __restrict__ ids, uint32_t* __restrict__ keys, uint32_t* __restrict__ pos) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) { keys[i] = (uint32_t)ids[i]; pos[i] = (uint32_t)i; }
-}
-
 // ACCUM: v_means holds the SH backward's direction gradient and is added to.
 template <bool ACCUM>
 __global__ __launch_bounds__(256) void surfel_preprocess_bwd_kernel(
@@ -563,19 +538,9 @@ extern "C" int gspl_rasterize_surfel_fwd(
         if (rc_sync != GSPL_OK) return rc_sync;
         n_isects = host[0];
         if (n_isects < 0) return fail_arg("rasterize_surfel_fwd: the list length never arrived");
-        if (n_isects > (int64_t)((1u << 30) - 1u)) {
-            set_error("rasterize_surfel_fwd", "more than 2^30-1 (tile, splat) intersections in one frame");
-            return GSPL_ERR_UNSUPPORTED;
-        }
-        if (n_isects > 0) {
-            const size_t ws2_bytes = gspl_bin_workspace_bytes(N, n_isects);
-            void* ws2 = alloc(alloc_ctx, GSPL_BUF_LISTS_WORK, ws2_bytes);
-            st->flatten_ids = (int32_t*)alloc(alloc_ctx, GSPL_BUF_LISTS, 4 * (size_t)n_isects);
-            if (!ws2 || !st->flatten_ids) return fail_arg("rasterize_surfel_fwd: allocation call-back returned NULL");
-            rc = gspl_bin_emit_sort(N, GSPL_MODE_INRIA, st->means2d, radii, nullptr, nullptr, order, cum, big_list, spans, 16, tile_w, tile_h, n_isects,
-                                    st->flatten_ids, st->offsets, ws2, ws2_bytes, stream);
-            if (rc != GSPL_OK) return rc;
-        }
+        rc = bin_lists_known(N, GSPL_MODE_INRIA, st->means2d, radii, nullptr, nullptr, order, cum, big_list, spans, 16, tile_w, tile_h, n_isects,
+                             alloc, alloc_ctx, &st->flatten_ids, st->offsets, stream, "rasterize_surfel_fwd");
+        if (rc != GSPL_OK) return rc;
     }
     st->n_isects = n_isects;
     hipLaunchKernelGGL(surfel_fwd_kernel, dim3(n_tiles), dim3(256), 0, s, width, height, tile_w, n_tiles, n_isects, st->offsets, st->flatten_ids,
@@ -609,19 +574,10 @@ extern "C" int gspl_rasterize_surfel_bwd(
     if (n_isects > 0) {
         const bool ordered = gspl_get_deterministic() != 0;
         float* entries = nullptr;
-        uint32_t* keys = nullptr;
-        void* sort_ws = nullptr;
-        size_t sort_ws_bytes = 0;
-        int id_bits = 1;
         if (ordered) {
             if (!alloc) return fail_arg("rasterize_surfel_bwd: the deterministic mode needs the allocation call-back");
-            while (id_bits < 32 && (1ll << id_bits) < (long long)N) ++id_bits;
-            sort_ws_bytes = gspl_radix_sort_workspace_bytes(n_isects, 4, 0, id_bits);
-            const size_t ent_bytes = up256((size_t)n_isects * SURF_GRAD * sizeof(float));
-            const size_t key_bytes = up256((size_t)n_isects * 4 * sizeof(uint32_t));
-            char* blk = (char*)alloc(alloc_ctx, GSPL_BUF_SURFEL_ENTRIES, ent_bytes + key_bytes + (sort_ws_bytes ? sort_ws_bytes : 16));
-            if (!blk) return fail_arg("rasterize_surfel_bwd: allocation call-back returned NULL");
-            entries = (float*)blk; keys = (uint32_t*)(blk + ent_bytes); sort_ws = blk + ent_bytes + key_bytes;
+            entries = (float*)alloc(alloc_ctx, GSPL_BUF_SURFEL_ENTRIES, ordered_scratch(N, n_isects, SURF_GRAD).total);
+            if (!entries) return fail_arg("rasterize_surfel_bwd: allocation call-back returned NULL");
             e = hipMemsetAsync(entries, 0, (size_t)n_isects * SURF_GRAD * sizeof(float), s);
             if (e != hipSuccess) return check_hip(e, "rasterize_surfel_bwd: clear");
         }
@@ -630,15 +586,8 @@ extern "C" int gspl_rasterize_surfel_bwd(
                            v_rows, entries);
         rc = check_launch("rasterize_surfel_bwd(composite)");
         if (rc != GSPL_OK) return rc;
-        if (ordered) {
-            uint32_t *k0 = keys, *k1 = keys + n_isects, *p0 = k1 + n_isects, *p1 = p0 + n_isects;
-            const unsigned grid = (unsigned)((n_isects + 255) / 256);
-            hipLaunchKernelGGL(surfel_iota_kernel, dim3(grid), dim3(256), 0, s, n_isects, st->flatten_ids, k0, p0);
-            int which = 0;
-            rc = gspl_radix_sort_pairs_u32(n_isects, k0, k1, p0, p1, 0, id_bits, &which, sort_ws, sort_ws_bytes, stream);
-            if (rc != GSPL_OK) return rc;
-            hipLaunchKernelGGL(surfel_ordered_reduce_kernel, dim3(grid), dim3(256), 0, s, n_isects, which ? k1 : k0, which ? p1 : p0, entries, v_rows);
-            rc = check_launch("rasterize_surfel_bwd(ordered reduce)");
+        if (ordered) {      // (v_rows is clear: the sums land as they are)
+            rc = ordered_reduce(N, n_isects, SURF_GRAD, st->flatten_ids, entries, v_rows, SURF_GRAD, s, "rasterize_surfel_bwd(ordered reduce)");
             if (rc != GSPL_OK) return rc;
         }
     }
