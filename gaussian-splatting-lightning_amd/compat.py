@@ -138,21 +138,13 @@ def install() -> list:
     _install_rasterizer_packages(installed)
     if _missing("simple_knn"):
         from . import ops
-        pkg = types.ModuleType("simple_knn")
-        pkg.__doc__ = "gspl_amd stand-in for simple_knn (HIP; see gspl_amd.ops.distCUDA2)"
-        sub = types.ModuleType("simple_knn._C")
-        sub.distCUDA2 = ops.distCUDA2
-        pkg._C = sub
+        pkg = _module("simple_knn", "gspl_amd stand-in for simple_knn (HIP; see gspl_amd.ops.distCUDA2)",
+                      _C=_module("simple_knn._C", None, distCUDA2=ops.distCUDA2))
         pkg.__path__ = []          # a package, so that `from simple_knn._C import ...` resolves through sys.modules
-        sys.modules["simple_knn"] = pkg
-        sys.modules["simple_knn._C"] = sub
         installed.append("simple_knn._C")
     if _missing("fused_ssim"):
         from . import ops
-        mod = types.ModuleType("fused_ssim")
-        mod.__doc__ = "gspl_amd stand-in for fused_ssim (HIP; see gspl_amd.ops.fused_ssim)"
-        mod.fused_ssim = ops.fused_ssim
-        sys.modules["fused_ssim"] = mod
+        _module("fused_ssim", "gspl_amd stand-in for fused_ssim (HIP; see gspl_amd.ops.fused_ssim)", fused_ssim=ops.fused_ssim)
         installed.append("fused_ssim")
     if _missing("fused_bilagrid"):
         _module("fused_bilagrid", "gspl_amd stand-in for fused_bilagrid (HIP; gspl_amd.bilagrid)",

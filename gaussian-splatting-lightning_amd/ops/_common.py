@@ -3,7 +3,7 @@ book-keeping of parameter updates in flight."""
 from __future__ import annotations
 
 import os
-from typing import NamedTuple, Optional, Sequence, Tuple
+from typing import Optional
 
 import torch
 from torch import Tensor
@@ -12,7 +12,7 @@ from .. import _lib as L
 from ._state import STATE as S
 
 _SUPPORTED_D = (1, 2, 3, 4, 8)
-_PACKED_ROW_STRIDE = int(__import__("os").environ.get("GSPL_PACKED_STRIDE", "0"))
+_PACKED_ROW_STRIDE = int(os.environ.get("GSPL_PACKED_STRIDE", "0"))
 
 
 def _packed_row_stride(nv: int) -> int:
@@ -80,6 +80,13 @@ def _grad_or_zeros(g: Optional[Tensor], like_shape, device) -> Tensor:
     return _f32c(g)
 
 
+def _attach_hit_mask(target, hit):
+    """`has_hit_any_pixels` on the caller's screen-space tensor: the flag bytes the kernels left (cleared, then only ever set to 1)
+    seen as bool, without a launch."""
+    if hit is not None and target is not None:
+        target.has_hit_any_pixels = hit.view(torch.bool)
+
+
 class _side_stream:
     """`with _side_stream(dev) as s:` runs the enclosed launches on a per-device side stream that first waits for everything
     already enqueued on the current stream; `s.join()` makes the current stream wait for them.  Set GSPL_SIDE_STREAM=0 to
@@ -90,7 +97,6 @@ class _side_stream:
     _torch: dict = {}
 
     def __init__(self, dev):
-        import os
         self.enabled = os.environ.get("GSPL_SIDE_STREAM", "1") != "0"
         self.dev = dev
         self.ctx = None

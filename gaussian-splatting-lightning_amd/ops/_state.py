@@ -78,6 +78,7 @@ class RuntimeState:
         # internal/optimizers.py:39); off by default: one more byte store per (tile, splat) in the hot kernel
         self.track_hit_pixels: bool = False
         # introspection for bench.py / tools: the last compositing forward leaves its per-splat inputs and tile lists in `last_raster`
+        # (a dict of tensors; nothing is copied)
         self.keep_last_raster: bool = False
         # the colour kernel on the library's lowest-priority stream instead of a default-priority torch stream (measured: no gain)
         self.side_low_priority: bool = env("GSPL_SIDE_LOW_PRIORITY", "0") != "0"

@@ -2,23 +2,20 @@
 emission and lists whose length stays on the device (`LazyLists`)."""
 from __future__ import annotations
 
-import os
-from typing import NamedTuple, Optional, Sequence, Tuple
+from typing import Optional
 
 import torch
 from torch import Tensor
 
 from .. import _lib as L
 from ._state import STATE as S
-from ._common import (_SUPPORTED_D, _packed_row_stride, _guarded, _f32c, _rows, _raw_ptr, _grad_or_zeros, _side_stream, colour_stream,
-                      join_pending_updates, _await_updates, _take_event)
+from ._common import _guarded, _f32c, _take_event
 
 # =============================================================================================
 # tile binning
 # =============================================================================================
 @_guarded(1)
 def _isect(mode: int, means2d: Tensor, radii: Tensor, depths: Tensor, tile_size: int, tile_w: int, tile_h: int):
-    lib = L.lib()
     means2d, depths = _f32c(means2d.detach()), _f32c(depths.detach())
     radii = radii.to(torch.int32).contiguous()
     N = means2d.shape[0]
@@ -28,9 +25,9 @@ def _isect(mode: int, means2d: Tensor, radii: Tensor, depths: Tensor, tile_size:
     if N == 0:
         z64 = torch.empty((0,), dtype=torch.int64, device=dev)
         return tiles, z64, torch.empty((0,), dtype=torch.int32, device=dev)
-    ws_bytes = lib.gspl_isect_workspace_bytes(N, 0)
+    ws_bytes = L.lib().gspl_isect_workspace_bytes(N, 0)
     if ws_bytes == 0:
-        raise RuntimeError("gspl_isect_workspace_bytes failed: " + lib.gspl_last_error().decode())
+        raise RuntimeError("gspl_isect_workspace_bytes failed: " + L.lib().gspl_last_error().decode())
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
     L.call("gspl_isect_count", N, mode, L.ptr(means2d), L.ptr(radii), tile_size, tile_w, tile_h,
                                  L.ptr(tiles), L.ptr(cum), L.ptr(ws), ws_bytes, L.stream())
@@ -38,7 +35,7 @@ def _isect(mode: int, means2d: Tensor, radii: Tensor, depths: Tensor, tile_size:
     isect_ids = torch.empty((n_isects,), dtype=torch.int64, device=dev)
     flatten_ids = torch.empty((n_isects,), dtype=torch.int32, device=dev)
     if n_isects > 0:
-        ws_bytes = lib.gspl_isect_workspace_bytes(N, n_isects)
+        ws_bytes = L.lib().gspl_isect_workspace_bytes(N, n_isects)
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
         L.call("gspl_isect_emit_sort", N, mode, L.ptr(means2d), L.ptr(radii), L.ptr(depths), L.ptr(cum),
                                          tile_size, tile_w, tile_h, n_isects, L.ptr(isect_ids), L.ptr(flatten_ids),
@@ -68,7 +65,6 @@ def isect_offset_encode(isect_ids: Tensor, n_cameras: int, tile_width: int, tile
     """gsplat-v1 signature (gsplat_v1_renderer.py:458) -> offsets [n_cameras, tile_height, tile_width] i32."""
     if n_cameras != 1:
         raise NotImplementedError("one camera per call")
-    lib = L.lib()
     offsets = torch.empty((1, tile_height, tile_width), dtype=torch.int32, device=isect_ids.device)
     isect_ids = isect_ids.contiguous()
     L.call("gspl_isect_offsets", isect_ids.shape[0], L.ptr(isect_ids) if isect_ids.numel() else None,
@@ -98,7 +94,6 @@ def bin_gaussians_begin(xys: Tensor, depths: Tensor, radii: Tensor, img_height: 
     before `bin_gaussians_end`, so the device is busy while the host waits for the one number that sizes the sort."""
     if block_width not in (8, 16, 32):
         raise NotImplementedError("block_width must be 8, 16 or 32 (the reference default is 16, gsplat_renderer.py:6)")
-    lib = L.lib()
     p = _PendingBins()
     p.block_width = block_width
     p.tile_w, p.tile_h = (img_width + block_width - 1) // block_width, (img_height + block_width - 1) // block_width
@@ -120,9 +115,9 @@ def bin_gaussians_begin(xys: Tensor, depths: Tensor, radii: Tensor, img_height: 
         p.cum = torch.empty((N + 1,), dtype=torch.int64, device=dev)      # scan [N] + the number of big splats
         p.big_list = torch.empty((N,), dtype=torch.int32, device=dev)     # depth-order indices of the splats taller than 16 tile rows
         p.spans = torch.empty((N, L.GSPL_BIN_SPAN_BYTES // 4), dtype=torch.int32, device=dev)
-        ws_bytes = lib.gspl_bin_workspace_bytes(N, 0)
+        ws_bytes = L.lib().gspl_bin_workspace_bytes(N, 0)
         if ws_bytes == 0:
-            raise RuntimeError("gspl_bin_workspace_bytes failed: " + lib.gspl_last_error().decode())
+            raise RuntimeError("gspl_bin_workspace_bytes failed: " + L.lib().gspl_last_error().decode())
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
         p.depths = depths
 
@@ -140,9 +135,9 @@ def bin_gaussians_begin(xys: Tensor, depths: Tensor, radii: Tensor, img_height: 
         guess = S.capacity.hint((dev.index, p.tile_w, p.tile_h), N)      # decayed running maximum per splat x N x margin (ops._state.ListCapacity)
         if S.speculative_emit and guess > 0:
             p.capacity = min(guess, MAX_ISECTS)
-            p.ws2_bytes = lib.gspl_bin_workspace_bytes(N, p.capacity)
+            p.ws2_bytes = L.lib().gspl_bin_workspace_bytes(N, p.capacity)
             if p.ws2_bytes == 0:
-                raise RuntimeError("gspl_bin_workspace_bytes failed: " + lib.gspl_last_error().decode())
+                raise RuntimeError("gspl_bin_workspace_bytes failed: " + L.lib().gspl_last_error().decode())
             p.ws2 = torch.empty((p.ws2_bytes,), dtype=torch.uint8, device=dev)
             _emit(p)
     return p
@@ -216,12 +211,11 @@ def _bin_count_arrived(p: _PendingBins) -> int:
 
 def _bin_finish(p: _PendingBins, n_isects: int):
     """Emission (again, if the guess was too low or there was none) and sort with the list length known to the host."""
-    lib = L.lib()
     N, dev = p.N, p.dev
     flat = torch.empty((n_isects,), dtype=torch.int32, device=dev)
     if n_isects > 0 and (p.ws2 is None or p.capacity < n_isects):
         p.capacity = n_isects
-        p.ws2_bytes = lib.gspl_bin_workspace_bytes(N, n_isects)
+        p.ws2_bytes = L.lib().gspl_bin_workspace_bytes(N, n_isects)
         p.ws2 = torch.empty((p.ws2_bytes,), dtype=torch.uint8, device=dev)
         _emit(p)
     L.call("gspl_bin_sort", N, p.tile_w, p.tile_h, n_isects, max(p.capacity, n_isects), L.ptr(flat) if n_isects else None, L.ptr(p.offsets),

@@ -1,28 +1,19 @@
 """Tile compositing (`rasterize_to_pixels`, `rasterize_gaussians`) and the per-splat score passes."""
 from __future__ import annotations
 
-import os
-from typing import NamedTuple, Optional, Sequence, Tuple
+from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
 
 from .. import _lib as L
 from ._state import STATE as S
-from ._common import (_SUPPORTED_D, _packed_row_stride, _guarded, _f32c, _rows, _raw_ptr, _grad_or_zeros, _side_stream, colour_stream,
-                      join_pending_updates, _await_updates, _take_event)
+from ._common import _SUPPORTED_D, _packed_row_stride, _guarded, _f32c, _grad_or_zeros, _attach_hit_mask
 from .binning import LazyLists, bin_gaussians
 
 # =============================================================================================
 # compositing
 # =============================================================================================
-# When True, the compositing backward also reports which splats some pixel actually composited and attaches the mask as
-# `has_hit_any_pixels` to the caller's screen-space tensor (the fork-only side channel gsplat's SelectiveAdam adapter
-# reads, internal/optimizers.py:39).  Off by default: it is one more byte store per (tile, splat) in the hot kernel.
-# Staged binning (`bin_gaussians`): with a speculative emission in flight the tile sort is enqueued before the host has read the
-# list length (False: wait for the count first, then sort — the round-1 order; kept for A/B runs and the tests of both orders).
-# Introspection for bench.py / tools: with S.keep_last_raster set, the last compositing forward leaves its per-splat inputs and
-# tile lists in S.last_raster (a dict of tensors; nothing is copied).
 
 
 class _CompositeFn(torch.autograd.Function):
@@ -30,7 +21,6 @@ class _CompositeFn(torch.autograd.Function):
     @_guarded(1)
     def forward(ctx, means2d, conics, colors, opacities, backgrounds, width, height, tile_size, offsets, flatten_ids,
                 absgrad, mode, layout, track_hits=False):
-        lib = L.lib()
         means2d_in = means2d
         means2d, conics, colors, opacities = map(_f32c, (means2d, conics, colors, opacities))
         backgrounds = _f32c(backgrounds)
@@ -72,8 +62,7 @@ class _CompositeFn(torch.autograd.Function):
                        N, n_isects, D, mode, layout, L.ptr(means2d), L.ptr(conics), L.ptr(colors), L.ptr(opacities), L.ptr(backgrounds),
                        width, height, tile_size, tile_w, tile_h, L.ptr(offsets), L.ptr(flatten_ids) if n_isects else None,
                        L.ptr(out), L.ptr(alphas), L.ptr(final_Ts), L.ptr(last_ids), L.ptr(hit), L.stream())
-        if hit is not None:
-            means2d_in.has_hit_any_pixels = hit.view(torch.bool)
+        _attach_hit_mask(means2d_in, hit)
         ctx.save_for_backward(means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids, final_Ts, last_ids)
         if S.keep_last_raster:
             S.last_raster = dict(mode=mode, width=width, height=height, means2d=means2d, conics=conics, opacities=opacities,
@@ -85,7 +74,6 @@ class _CompositeFn(torch.autograd.Function):
     @staticmethod
     @_guarded(0)
     def backward(ctx, v_out, v_alphas):
-        lib = L.lib()
         means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids, final_Ts, last_ids = ctx.saved_tensors
         width, height, tile_size, tile_w, tile_h, absgrad, mode, layout = ctx.cfg
         N, D = colors.shape
@@ -102,8 +90,7 @@ class _CompositeFn(torch.autograd.Function):
                 N, n_isects, D, mode, layout, L.ptr(means2d), L.ptr(conics), L.ptr(colors), L.ptr(opacities), L.ptr(backgrounds),
                 width, height, tile_size, tile_w, tile_h, L.ptr(offsets), L.ptr(flatten_ids), L.ptr(final_Ts), L.ptr(last_ids),
                 L.ptr(v_out), L.ptr(v_alphas), L.ptr(packed), RS, 1 if absgrad else 0, L.ptr(hit), L.stream())
-            if hit is not None:
-                ctx.means2d_ref.has_hit_any_pixels = hit.bool()
+            _attach_hit_mask(ctx.means2d_ref, hit)
         v_means2d, v_conics, v_opac, v_colors = packed[:, 0:2], packed[:, 2:5], packed[:, 5], packed[:, 6:6 + D]
         v_abs = packed[:, 6 + D:8 + D] if absgrad else None
         if absgrad:

@@ -1,8 +1,9 @@
 """The Inria API: `GaussianRasterizationSettings`, `GaussianRasterizer` (one fused C call per direction, or the staged calls)."""
 from __future__ import annotations
 
-import os
-from typing import NamedTuple, Optional, Sequence, Tuple
+import ctypes
+from collections import namedtuple
+from typing import NamedTuple
 
 import torch
 from torch import Tensor
@@ -10,10 +11,8 @@ from torch import Tensor
 from .. import _lib as L
 from ._state import STATE as S
 from ._frame import FrameBlocks
-from ._common import (_SUPPORTED_D, _packed_row_stride, _guarded, _f32c, _rows, _raw_ptr, _grad_or_zeros, _side_stream, colour_stream,
-                      join_pending_updates, _await_updates, _take_event)
+from ._common import _packed_row_stride, _guarded, _f32c, _grad_or_zeros, _side_stream, colour_stream, _await_updates, _attach_hit_mask
 from .binning import MAX_ISECTS, bin_gaussians_begin, bin_gaussians_end
-from .compositing import _CompositeFn, _composite
 
 # =============================================================================================
 # Inria API  (diff_gaussian_rasterization.GaussianRasterizer)
@@ -31,6 +30,24 @@ class GaussianRasterizationSettings(NamedTuple):
     campos: Tensor
     prefiltered: bool = False
     debug: bool = False
+
+
+# `diff_accel_gaussian_rasterization.GaussianRasterizationSettings` (the Taming 3DGS rasterizer package,
+# internal/renderers/taming_3dgs_renderer.py:4): the Inria fields and `antialiasing`
+AccelRasterizationSettings = namedtuple("AccelRasterizationSettings", GaussianRasterizationSettings._fields + ("antialiasing",),
+                                        defaults=(*GaussianRasterizationSettings._field_defaults.values(), False))
+
+
+def _check_inputs(shs, colors_precomp, *geometry):
+    """Upstream's input check, its messages verbatim; `geometry`: (scales, rotations, cov3D_precomp) where a precomputed covariance is
+    an alternative to the scale/rotation pair."""
+    if (shs is None) == (colors_precomp is None):
+        raise Exception("Please provide excatly one of either SHs or precomputed colors!")
+    if geometry:
+        scales, rotations, cov3D_precomp = geometry
+        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+            raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
 
 
 def _split_sh(sh, sh_rest):
@@ -51,6 +68,16 @@ def _split_sh(sh, sh_rest):
     return sh, sh_rest, 1 + sh_rest.shape[1]
 
 
+def _forward_inputs(means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, s, sh_rest):
+    """The shared opening of the two forwards: every input float32 and contiguous, opacities flat, the SH pair split."""
+    means3D = _f32c(means3D)
+    sh, colors_precomp, scales, rotations, cov3D_precomp = map(_f32c, (sh, colors_precomp, scales, rotations, cov3D_precomp))
+    opac = _f32c(opacities).reshape(-1)
+    viewm, projm, campos, bg = _f32c(s.viewmatrix), _f32c(s.projmatrix), _f32c(s.campos), _f32c(s.bg)
+    sh, sh_rest, n_coeffs = _split_sh(sh, sh_rest)
+    return means3D, sh, sh_rest, n_coeffs, colors_precomp, opac, scales, rotations, cov3D_precomp, viewm, projm, campos, bg
+
+
 class _InriaRasterizeFn(torch.autograd.Function):
     """The stage-by-stage orchestration (GSPL_FUSED_INRIA=0).  It implements the plain rasterizer only: anti-aliasing and the
     inverse-depth channel (`diff_accel_gaussian_rasterization`, GSPL_INRIA_ANTIALIAS / GSPL_INRIA_INVDEPTH) exist in the fused call
@@ -59,17 +86,12 @@ class _InriaRasterizeFn(torch.autograd.Function):
     @staticmethod
     @_guarded(1)
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, settings, sh_rest=None):
-        lib = L.lib()
         s: GaussianRasterizationSettings = settings
         dev = means3D.device
-        means3D = _f32c(means3D)
+        means3D, sh, sh_rest, n_coeffs, colors_precomp, opac, scales, rotations, cov3D_precomp, viewm, projm, campos, bg = _forward_inputs(
+            means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, s, sh_rest)
         N = means3D.shape[0]
         H, W = int(s.image_height), int(s.image_width)
-        sh, colors_precomp, scales, rotations, cov3D_precomp = map(_f32c, (sh, colors_precomp, scales, rotations, cov3D_precomp))
-        opac = _f32c(opacities).reshape(-1)
-        viewm, projm, campos = _f32c(s.viewmatrix), _f32c(s.projmatrix), _f32c(s.campos)
-        bg = _f32c(s.bg)
-        sh, sh_rest, n_coeffs = _split_sh(sh, sh_rest)
         radii = torch.empty((N,), dtype=torch.int32, device=dev)
         means2d = torch.empty((N, 2), dtype=torch.float32, device=dev)
         depths = torch.empty((N,), dtype=torch.float32, device=dev)
@@ -124,7 +146,6 @@ class _InriaRasterizeFn(torch.autograd.Function):
     @staticmethod
     @_guarded(0)
     def backward(ctx, v_out, _v_radii):
-        lib = L.lib()
         (means3D, scales, rotations, cov3D_precomp, sh, opac, viewm, projm, campos, bg,
          radii, means2d, conics, colors, clamped, cov3d, offsets, flat, final_Ts, last_ids, sh_jac, sh_rest) = ctx.saved_tensors
         H, W, tile, tile_w, tile_h, degree, n_coeffs, tanfovx, tanfovy, scale_modifier, has_precomp_colors, opac_shape = ctx.cfg
@@ -140,8 +161,7 @@ class _InriaRasterizeFn(torch.autograd.Function):
                 N, n_isects, 3, L.GSPL_MODE_INRIA, L.GSPL_LAYOUT_CHW, L.ptr(means2d), L.ptr(conics), L.ptr(colors), L.ptr(opac),
                 L.ptr(bg), W, H, tile, tile_w, tile_h, L.ptr(offsets), L.ptr(flat), L.ptr(final_Ts), L.ptr(last_ids),
                 L.ptr(v_out), None, L.ptr(packed), RS, 0, L.ptr(hit), L.stream())
-            if hit is not None and ctx.means2D_ref is not None:
-                ctx.means2D_ref.has_hit_any_pixels = hit.bool()
+            _attach_hit_mask(ctx.means2D_ref, hit)
         v_opac = torch.empty((N,), dtype=torch.float32, device=dev)      # dense copy of the packed column (written below)
         v_means = torch.empty((N, 3), dtype=torch.float32, device=dev)
         v_ndc = torch.empty((N, 3), dtype=torch.float32, device=dev)
@@ -178,16 +198,12 @@ class _InriaFusedFn(torch.autograd.Function):
         kernels (GSPL_INRIA_RAW_PARAMS) and the backward returns the raw parameters' gradients.
         antialias: the composited opacity is opacity * sqrt(max(2.5e-5, det0 / det1)) (GSPL_INRIA_ANTIALIAS).
         invdepth: the output is [4,H,W], colour and the composited inverse view-space depth (background 0; GSPL_INRIA_INVDEPTH)."""
-        import ctypes
         s: GaussianRasterizationSettings = settings
         dev = means3D.device
-        means3D = _f32c(means3D)
+        means3D, sh, sh_rest, n_coeffs, colors_precomp, opac, scales, rotations, cov3D_precomp, viewm, projm, campos, bg = _forward_inputs(
+            means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, s, sh_rest)
         N = means3D.shape[0]
         H, W = int(s.image_height), int(s.image_width)
-        sh, colors_precomp, scales, rotations, cov3D_precomp = map(_f32c, (sh, colors_precomp, scales, rotations, cov3D_precomp))
-        opac = _f32c(opacities).reshape(-1)
-        viewm, projm, campos, bg = _f32c(s.viewmatrix), _f32c(s.projmatrix), _f32c(s.campos), _f32c(s.bg)
-        sh, sh_rest, n_coeffs = _split_sh(sh, sh_rest)
         D = 4 if invdepth else 3
         if invdepth:      # the inverse-depth channel's background is 0
             bg = torch.cat([bg.reshape(-1)[:3], bg.new_zeros(1)])
@@ -263,7 +279,6 @@ class _InriaFusedFn(torch.autograd.Function):
     @staticmethod
     @_guarded(0)
     def backward(ctx, v_out, _v_radii):
-        import ctypes
         means3D, scales, rotations, sh, opac, viewm, projm, campos, bg, radii, sh_rest, *saved_blocks = ctx.saved_tensors      # (a released graph raises here)
         blocks = ctx.frame.unpack(saved_blocks)
         H, W, degree, n_coeffs, tanfovx, tanfovy, scale_modifier, has_precomp_colors, use_cov, opac_shape, D = ctx.cfg
@@ -296,50 +311,44 @@ class _InriaFusedFn(torch.autograd.Function):
         # backward apply its update themselves (gspl_rasterize_inria_bwd_adam) and no parameter gradient is written or returned
         # (not for a frame with anti-aliasing or inverse depth: gspl_rasterize_inria_bwd_adam refuses them, the optimizer then steps itself)
         extended = bool(ctx.state.flags & (L.GSPL_INRIA_ANTIALIAS | L.GSPL_INRIA_INVDEPTH))
+        plan = None
         if S.backward_optimizers and N > 0 and not use_cov and not has_precomp_colors and not extended:
             need = ctx.needs_input_grad
             if need[0] and need[2] and need[4] and need[5] and need[6] and (sh_rest is None or need[9]):
                 from ..optimizers import claim_backward_update
                 plan = claim_backward_update(dict(means=means3D, scales=scales, rotations=rotations, opacities=opac, shs=sh, shs_rest=sh_rest))
-                if plan is not None:
-                    scratch, v_ndc = E(N, 3), E(N, 3)
-                    try:
-                        with torch.cuda.device(dev):
-                            L.call("gspl_rasterize_inria_bwd_adam", degree, n_coeffs, L.ptr(means3D), L.ptr(scales), L.ptr(rotations), L.ptr(sh),
-                                   L.ptr(sh_rest), L.ptr(opac), L.ptr(viewm), L.ptr(projm), L.ptr(campos), L.ptr(bg), tanfovx, tanfovy, scale_modifier,
-                                   L.ptr(radii), ctypes.byref(ctx.state), L.ptr(v_out), L.ptr(packed), L.ptr(hit), L.ptr(scratch), L.ptr(v_ndc),
-                                   ctypes.byref(plan), L.stream())
-                    except Exception:
-                        _poison(ctx, stats)
-                        raise
-                    if stats is not None:
-                        stats.applied = True
-                        ctx.state.stats_accum = ctx.state.stats_denom = ctx.state.stats_max_radii = None
-                    if hit is not None and ctx.means2D_ref is not None:
-                        ctx.means2D_ref.has_hit_any_pixels = hit.view(torch.bool)
-                    return None, v_ndc, None, None, None, None, None, None, None, None, None, None, None
-        v_means, v_ndc, v_opac = E(N, 3), E(N, 3), E(N)
-        v_scales = None if use_cov else E(N, 3)
-        v_quats = None if use_cov else E(N, 4)
-        v_cov = E(N, 6) if use_cov else None
-        v_sh = None if has_precomp_colors else torch.empty_like(sh)
-        v_sh_rest = None if sh_rest is None else torch.empty_like(sh_rest)
-        v_cp = E(N, 3) if has_precomp_colors else None
+        if plan is not None:
+            scratch, v_ndc = E(N, 3), E(N, 3)
+        else:
+            v_means, v_ndc, v_opac = E(N, 3), E(N, 3), E(N)
+            v_scales = None if use_cov else E(N, 3)
+            v_quats = None if use_cov else E(N, 4)
+            v_cov = E(N, 6) if use_cov else None
+            v_sh = None if has_precomp_colors else torch.empty_like(sh)
+            v_sh_rest = None if sh_rest is None else torch.empty_like(sh_rest)
+            v_cp = E(N, 3) if has_precomp_colors else None
         if N > 0:
             try:
                 with torch.cuda.device(dev):
-                    L.call("gspl_rasterize_inria_bwd", degree, n_coeffs, L.ptr(means3D), L.ptr(scales), L.ptr(rotations), L.ptr(sh), L.ptr(sh_rest),
-                           L.ptr(opac), L.ptr(viewm), L.ptr(projm), L.ptr(campos), L.ptr(bg), tanfovx, tanfovy, scale_modifier, L.ptr(radii),
-                           ctypes.byref(ctx.state), L.ptr(v_out), L.ptr(packed), L.ptr(hit), L.ptr(v_means), L.ptr(v_ndc), L.ptr(v_sh), L.ptr(v_sh_rest),
-                           L.ptr(v_cp), L.ptr(v_opac), L.ptr(v_scales), L.ptr(v_quats), L.ptr(v_cov), L.stream())
+                    if plan is not None:
+                        L.call("gspl_rasterize_inria_bwd_adam", degree, n_coeffs, L.ptr(means3D), L.ptr(scales), L.ptr(rotations), L.ptr(sh),
+                               L.ptr(sh_rest), L.ptr(opac), L.ptr(viewm), L.ptr(projm), L.ptr(campos), L.ptr(bg), tanfovx, tanfovy, scale_modifier,
+                               L.ptr(radii), ctypes.byref(ctx.state), L.ptr(v_out), L.ptr(packed), L.ptr(hit), L.ptr(scratch), L.ptr(v_ndc),
+                               ctypes.byref(plan), L.stream())
+                    else:
+                        L.call("gspl_rasterize_inria_bwd", degree, n_coeffs, L.ptr(means3D), L.ptr(scales), L.ptr(rotations), L.ptr(sh), L.ptr(sh_rest),
+                               L.ptr(opac), L.ptr(viewm), L.ptr(projm), L.ptr(campos), L.ptr(bg), tanfovx, tanfovy, scale_modifier, L.ptr(radii),
+                               ctypes.byref(ctx.state), L.ptr(v_out), L.ptr(packed), L.ptr(hit), L.ptr(v_means), L.ptr(v_ndc), L.ptr(v_sh), L.ptr(v_sh_rest),
+                               L.ptr(v_cp), L.ptr(v_opac), L.ptr(v_scales), L.ptr(v_quats), L.ptr(v_cov), L.stream())
             except Exception:
                 _poison(ctx, stats)
                 raise
             if stats is not None:
                 stats.applied = True
                 ctx.state.stats_accum = ctx.state.stats_denom = ctx.state.stats_max_radii = None
-            if hit is not None and ctx.means2D_ref is not None:
-                ctx.means2D_ref.has_hit_any_pixels = hit.view(torch.bool)
+            _attach_hit_mask(ctx.means2D_ref, hit)
+            if plan is not None:
+                return None, v_ndc, None, None, None, None, None, None, None, None, None, None, None
             if S.keep_last_raster and S.last_raster is not None:
                 # introspection (tests): the compositing backward's own per-splat rows, x y | a b c | opacity | r g b
                 S.last_raster["packed_grads"] = packed
@@ -358,10 +367,28 @@ def _poison(ctx, stats):
         stats.applied = True
 
 
-def _mark_fused(out):
-    """The radii of a fused call say so: its backward can take the frame's densification statistics along (density.py)."""
-    out[1]._gspl_fused_inria = True
-    return out
+def _rasterize(settings, means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, shs_rest, raw_parameters,
+               antialiasing=False, inverse_depth=False):
+    """The one way into the two autograd functions, for `GaussianRasterizer` and `rasterize_inria_accel`: checks the inputs, drops an
+    empty `shs_rest`, and makes one C-ABI call per direction (csrc/fused.hip) unless GSPL_FUSED_INRIA=0 selects the stage-by-stage
+    orchestration.  The radii of a fused call say so: its backward can take the frame's densification statistics along (density.py)."""
+    if isinstance(shs, (tuple, list)):
+        shs, shs_rest = shs
+    _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
+    if not S.fused_inria and (antialiasing or inverse_depth):
+        raise NotImplementedError("anti-aliasing and inverse depth exist in the fused Inria call only (GSPL_FUSED_INRIA=0 selects the staged one)")
+    if shs_rest is not None and shs_rest.shape[1] == 0:
+        shs_rest = None
+    if raw_parameters and cov3D_precomp is not None:
+        raise Exception("raw_parameters needs the scale/rotation pair")
+    if S.fused_inria:
+        out = _InriaFusedFn.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, settings, shs_rest,
+                                  bool(raw_parameters), bool(antialiasing), bool(inverse_depth))
+        out[1]._gspl_fused_inria = True
+        return out
+    if raw_parameters:      # the stage-by-stage orchestration takes activated values: the same three activations through torch
+        opacities, scales, rotations = torch.sigmoid(opacities), torch.exp(scales), torch.nn.functional.normalize(rotations)
+    return _InriaRasterizeFn.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, settings, shs_rest)
 
 
 class GaussianRasterizer(torch.nn.Module):
@@ -380,26 +407,8 @@ class GaussianRasterizer(torch.nn.Module):
         unnormalised quaternions — and the activations of the reference's model (sigmoid / exp / F.normalize,
         internal/models/vanilla_gaussian.py:345-358) run inside the preprocess kernels, forward and backward, instead of as ten torch
         launches and a reduction per step around the call."""
-        if isinstance(shs, (tuple, list)):
-            shs, shs_rest = shs
-        if (shs is None) == (colors_precomp is None):
-            raise Exception("Please provide excatly one of either SHs or precomputed colors!")
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
-        # one C-ABI call per direction (csrc/fused.hip) unless GSPL_FUSED_INRIA=0 selects the stage-by-stage orchestration
-        fn = _InriaFusedFn if S.fused_inria else _InriaRasterizeFn
-        if shs_rest is not None and shs_rest.shape[1] == 0:
-            shs_rest = None
-        if raw_parameters:
-            if cov3D_precomp is not None:
-                raise Exception("raw_parameters needs the scale/rotation pair")
-            if S.fused_inria:
-                return _mark_fused(fn.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, None, self.raster_settings, shs_rest, True))
-            # the stage-by-stage orchestration takes activated values: the same three activations through torch
-            opacities, scales, rotations = torch.sigmoid(opacities), torch.exp(scales), torch.nn.functional.normalize(rotations)
-        out = fn.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, self.raster_settings, shs_rest)
-        return _mark_fused(out) if fn is _InriaFusedFn else out
+        return _rasterize(self.raster_settings, means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, shs_rest,
+                          raw_parameters)
 
 
 def rasterize_inria_accel(settings: GaussianRasterizationSettings, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None,
@@ -409,44 +418,11 @@ def rasterize_inria_accel(settings: GaussianRasterizationSettings, means3D, mean
     2D filter, GSPL_INRIA_ANTIALIAS) and `inverse_depth` (a 4th composited channel 1 / z, GSPL_INRIA_INVDEPTH).  Returns (color [3,H,W],
     radii [N] i32, inverse depth [1,H,W] or None); the two images are views of one [4,H,W] output.  Arguments as `GaussianRasterizer`.
     There is no stage-by-stage form of these switches: with GSPL_FUSED_INRIA=0 they raise NotImplementedError."""
-    if (shs is None) == (colors_precomp is None):
-        raise Exception("Please provide excatly one of either SHs or precomputed colors!")
-    if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-            ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-        raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
-    if not S.fused_inria:
-        if antialiasing or inverse_depth:
-            raise NotImplementedError("anti-aliasing and inverse depth exist in the fused Inria call only (GSPL_FUSED_INRIA=0 selects the staged one)")
-        out, radii = GaussianRasterizer(settings)(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp,
-                                                  shs_rest=shs_rest, raw_parameters=raw_parameters)
-        return out, radii, None
-    if raw_parameters and cov3D_precomp is not None:
-        raise Exception("raw_parameters needs the scale/rotation pair")
-    if shs_rest is not None and shs_rest.shape[1] == 0:
-        shs_rest = None
-    out, radii = _mark_fused(_InriaFusedFn.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, settings,
-                                                 shs_rest, bool(raw_parameters), bool(antialiasing), bool(inverse_depth)))
+    out, radii = _rasterize(settings, means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, shs_rest,
+                            raw_parameters, antialiasing, inverse_depth)
     if inverse_depth:
         return out[:3], radii, out[3:]
     return out, radii, None
-
-
-# ---- diff_accel_gaussian_rasterization (the Taming 3DGS rasterizer package, internal/renderers/taming_3dgs_renderer.py:4) -------------
-class AccelRasterizationSettings(NamedTuple):
-    """`diff_accel_gaussian_rasterization.GaussianRasterizationSettings`: the Inria fields and `antialiasing`."""
-    image_height: int
-    image_width: int
-    tanfovx: float
-    tanfovy: float
-    bg: Tensor
-    scale_modifier: float
-    viewmatrix: Tensor
-    projmatrix: Tensor
-    sh_degree: int
-    campos: Tensor
-    prefiltered: bool = False
-    debug: bool = False
-    antialiasing: bool = False
 
 
 class AccelGaussianRasterizer(torch.nn.Module):
@@ -462,14 +438,13 @@ class AccelGaussianRasterizer(torch.nn.Module):
 
     def forward(self, means3D, means2D, dc=None, shs=None, colors_precomp=None, opacities=None, scales=None, rotations=None, cov3D_precomp=None,
                 raw_parameters: bool = False):
-        if colors_precomp is None and dc is None and shs is None:
-            raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if colors_precomp is not None:
             sh, sh_rest = None, None
         elif dc is None:
             sh, sh_rest = shs, None
         else:
             sh, sh_rest = dc, shs
+        _check_inputs(sh, colors_precomp)
         return rasterize_inria_accel(self.raster_settings, means3D, means2D, opacities, sh, colors_precomp, scales, rotations, cov3D_precomp,
                                      shs_rest=sh_rest, raw_parameters=raw_parameters,
                                      antialiasing=bool(getattr(self.raster_settings, "antialiasing", False)), inverse_depth=True)

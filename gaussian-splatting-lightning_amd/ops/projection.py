@@ -1,16 +1,14 @@
 """Projection (`fully_fused_projection`, `project_gaussians`) and SH colours (`spherical_harmonics*`, `sh_view_colors*`)."""
 from __future__ import annotations
 
-import os
-from typing import NamedTuple, Optional, Sequence, Tuple
+from typing import Optional
 
 import torch
 from torch import Tensor
 
 from .. import _lib as L
 from ._state import STATE as S
-from ._common import (_SUPPORTED_D, _packed_row_stride, _guarded, _f32c, _rows, _raw_ptr, _grad_or_zeros, _side_stream, colour_stream,
-                      join_pending_updates, _await_updates, _take_event)
+from ._common import _guarded, _f32c, _rows, _raw_ptr, _grad_or_zeros, _await_updates
 
 # =============================================================================================
 # projection
@@ -20,7 +18,6 @@ class _ProjectFn(torch.autograd.Function):
     @_guarded(1)
     def forward(ctx, means, scales, quats, viewmats, Ks, width, height, tile_size, scale_modifier,
                 eps2d, near_plane, far_plane, radius_clip, calc_compensations, want_tiles, camera_model=0, want_cov3d=False):
-        lib = L.lib()
         means, scales, quats, viewmats, Ks = map(_f32c, (means, scales, quats, viewmats, Ks))
         C, N = viewmats.shape[0], means.shape[0]
         dev = means.device
@@ -53,7 +50,6 @@ class _ProjectFn(torch.autograd.Function):
     @staticmethod
     @_guarded(0)
     def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, v_comps, _v_tiles, _v_cov3d=None):
-        lib = L.lib()
         means, scales, quats, viewmats, Ks, radii = ctx.saved_tensors
         width, height, scale_modifier, eps2d, calc_comp, camera_model = ctx.cfg
         C, N = radii.shape
@@ -172,7 +168,6 @@ class _SHFn(torch.autograd.Function):
     @_guarded(2)
     def forward(ctx, degree, dirs, origin, dc, rest, masks, flags):
         """dc: [N,K,3] merged (rest is None) or [N,1,3]; rest: [N,K-1,3] or None."""
-        lib = L.lib()
         dirs, dc, rest = _f32c(dirs), _f32c(dc), _f32c(rest)
         origin = _f32c(origin)
         N = dirs.shape[0]
@@ -206,7 +201,6 @@ class _SHFn(torch.autograd.Function):
     @staticmethod
     @_guarded(0)
     def backward(ctx, v_colors):
-        lib = L.lib()
         dirs, origin, dc, rest, mask8, clamped = ctx.saved_tensors
         degree, flags, merged, n_coeffs, dc_stride, rest_stride = ctx.cfg
         N = dirs.shape[0]

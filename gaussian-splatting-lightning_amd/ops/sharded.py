@@ -1,16 +1,14 @@
 """The Gaussian-sharded renderer's pieces: the 48-byte visible-splat records and the step as three autograd nodes."""
 from __future__ import annotations
 
-import os
-from typing import NamedTuple, Optional, Sequence, Tuple
+from typing import Optional, Sequence
 
 import torch
 from torch import Tensor
 
 from .. import _lib as L
 from ._state import STATE as S
-from ._common import (_SUPPORTED_D, _packed_row_stride, _guarded, _f32c, _rows, _raw_ptr, _grad_or_zeros, _side_stream, colour_stream,
-                      join_pending_updates, _await_updates, _take_event)
+from ._common import _guarded, _f32c, _rows, _raw_ptr, _take_event
 from .projection import _ProjectFn, _SHBatchedFn
 from .binning import bin_gaussians
 from .compositing import _CompositeFn
@@ -64,7 +62,6 @@ class _PackRecordsFn(torch.autograd.Function):
     @staticmethod
     @_guarded(3)
     def forward(ctx, C, has_comp, opacities, *flat):
-        lib = L.lib()
         groups = [flat[k * C:(k + 1) * C] for k in range(6)]
         radii = _batched(groups[0])
         if radii.dtype != torch.int32:
@@ -80,7 +77,7 @@ class _PackRecordsFn(torch.autograd.Function):
         ends = torch.empty((C,), dtype=torch.int64, device=dev)
         pool = S.pinned_ends.setdefault(C, [])
         host_ends = pool.pop() if pool else torch.empty((C,), dtype=torch.int64).pin_memory()
-        ws_bytes = lib.gspl_records_workspace_bytes(C, N)
+        ws_bytes = L.lib().gspl_records_workspace_bytes(C, N)
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
         L.call("gspl_records_pack_fwd", C, N, L.ptr(radii), L.ptr(means2d), L.ptr(depths), L.ptr(conics), L.ptr(comps), L.ptr(opac), L.ptr(rgbs),
                L.ptr(records), L.ptr(slots), L.ptr(ends), host_ends.data_ptr(), L.ptr(ws), ws_bytes, L.stream())
@@ -300,7 +297,6 @@ class _ShardFrontFn(torch.autograd.Function):
         proj, sh, pack = _StageCtx(), _StageCtx(), _StageCtx()
         radii, means2d, depths, conics, comps, _, _ = _ProjectFn.forward(
             proj, means, scales, quats, viewmats, Ks, width, height, 16, 1.0, eps2d, 0.01, 1e10, 0.0, True, False, L.GSPL_CAMERA_PINHOLE, False)
-        lib = L.lib()
         N, dev = means.shape[0], radii.device
         opac = _f32c(opacities.detach()).reshape(-1)
         assert opac.shape[0] == N
@@ -321,7 +317,7 @@ class _ShardFrontFn(torch.autograd.Function):
             ends_dev = torch.empty((C,), dtype=torch.int64, device=dev)
             pool = S.pinned_ends.setdefault(C, [])
             host_ends = pool.pop() if pool else torch.empty((C,), dtype=torch.int64).pin_memory()
-            ws_bytes = lib.gspl_records_workspace_bytes(C, N)
+            ws_bytes = L.lib().gspl_records_workspace_bytes(C, N)
             ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
             L.call("gspl_records_count_fwd", C, N, L.ptr(radii), L.ptr(slots), L.ptr(ends_dev), host_ends.data_ptr(), L.ptr(ws), ws_bytes, L.stream())
             ev = _take_event(dev)

@@ -1,29 +1,23 @@
 """Side functions of the path: radix sort wrappers, `distCUDA2`, the fused photometric loss."""
 from __future__ import annotations
 
-import os
-from typing import NamedTuple, Optional, Sequence, Tuple
-
 import torch
 from torch import Tensor
 
 from .. import _lib as L
-from ._state import STATE as S
-from ._common import (_SUPPORTED_D, _packed_row_stride, _guarded, _f32c, _rows, _raw_ptr, _grad_or_zeros, _side_stream, colour_stream,
-                      join_pending_updates, _await_updates, _take_event)
+from ._common import _f32c
 
 # =============================================================================================
 # radix sort of the binning stage (exported for the parity tests)
 # =============================================================================================
 def _radix_sort(fn: str, keys: Tensor, vals, begin_bit: int, end_bit: int):
     import ctypes
-    lib = L.lib()
     n = keys.numel()
     k0, k1 = keys.clone(), torch.empty_like(keys)
     v0 = v1 = None
     if vals is not None:
         v0, v1 = vals.clone(), torch.empty_like(vals)
-    ws_bytes = lib.gspl_radix_sort_workspace_bytes(n, keys.element_size(), begin_bit, end_bit)
+    ws_bytes = L.lib().gspl_radix_sort_workspace_bytes(n, keys.element_size(), begin_bit, end_bit)
     if ws_bytes == 0:
         raise RuntimeError("gspl_radix_sort_workspace_bytes: unsupported size or bit range")
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=keys.device)
@@ -56,7 +50,6 @@ def radix_sort_keys64(keys: Tensor, begin_bit: int, end_bit: int) -> Tensor:
 def distCUDA2(points: Tensor) -> Tensor:
     """Drop-in for `simple_knn._C.distCUDA2` (reference call site: internal/models/vanilla_gaussian.py:122-124):
     points [N,3] on the GPU -> [N] mean squared distance to the three nearest other points (fp32)."""
-    lib = L.lib()
     if not points.is_cuda:
         raise RuntimeError("distCUDA2: points must be on the GPU (the reference calls it with `.cuda()`)")
     pts = _f32c(points.detach()).reshape(-1, 3)
@@ -64,9 +57,9 @@ def distCUDA2(points: Tensor) -> Tensor:
     out = torch.empty((N,), dtype=torch.float32, device=pts.device)
     if N == 0:
         return out
-    ws_bytes = lib.gspl_knn_workspace_bytes(N)
+    ws_bytes = L.lib().gspl_knn_workspace_bytes(N)
     if ws_bytes == 0:
-        raise RuntimeError("gspl_knn_workspace_bytes failed: " + lib.gspl_last_error().decode())
+        raise RuntimeError("gspl_knn_workspace_bytes failed: " + L.lib().gspl_last_error().decode())
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=pts.device)
     with torch.cuda.device(pts.device):
         L.call("gspl_knn3_mean_dist2", N, L.ptr(pts), L.ptr(out), L.ptr(ws), ws_bytes, L.stream())
@@ -82,7 +75,6 @@ class _L1SSIMFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, img1, img2, train):
-        lib = L.lib()
         if not img1.is_cuda or not img2.is_cuda:
             raise RuntimeError("l1_ssim: images must be on the GPU")
         if img1.shape != img2.shape or img1.dim() < 2:
@@ -96,7 +88,7 @@ class _L1SSIMFn(torch.autograd.Function):
         means = torch.empty((2,), dtype=torch.float32, device=dev)
         keep = bool(train) and img1.requires_grad
         maps = torch.empty((3, planes, H, W), dtype=torch.float32, device=dev) if keep else None
-        ws_bytes = lib.gspl_loss_workspace_bytes(planes, H, W)
+        ws_bytes = L.lib().gspl_loss_workspace_bytes(planes, H, W)
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
             L.call("gspl_loss_l1_ssim_fwd", planes, H, W, L.ptr(x), L.ptr(y), L.ptr(means),
@@ -142,7 +134,6 @@ class _PhotometricLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, img1, img2, w_l1, w_ssim):
-        lib = L.lib()
         if not img1.is_cuda or not img2.is_cuda:
             raise RuntimeError("photometric_loss: images must be on the GPU")
         if img1.shape != img2.shape or img1.dim() < 2:
@@ -156,7 +147,7 @@ class _PhotometricLossFn(torch.autograd.Function):
         means = torch.empty((3,), dtype=torch.float32, device=dev)          # (L1, SSIM, weighted loss)
         keep = img1.requires_grad
         maps = torch.empty((3, planes, H, W), dtype=torch.float32, device=dev) if keep else None
-        ws_bytes = lib.gspl_loss_workspace_bytes(planes, H, W)
+        ws_bytes = L.lib().gspl_loss_workspace_bytes(planes, H, W)
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
             L.call("gspl_loss_photometric_fwd", planes, H, W, L.ptr(x), L.ptr(y), float(w_l1), float(w_ssim), L.ptr(means),

@@ -7,29 +7,13 @@ distortion.  `means2D.grad` receives upstream's densification proxy (include/gsp
 from __future__ import annotations
 
 import ctypes
-from typing import NamedTuple
 
 import torch
-from torch import Tensor
 
 from .. import _lib as L
 from ._common import _guarded, _f32c, _grad_or_zeros
 from ._frame import FrameBlocks
-
-
-class SurfelRasterizationSettings(NamedTuple):
-    image_height: int
-    image_width: int
-    tanfovx: float
-    tanfovy: float
-    bg: Tensor
-    scale_modifier: float
-    viewmatrix: Tensor
-    projmatrix: Tensor
-    sh_degree: int
-    campos: Tensor
-    prefiltered: bool = False
-    debug: bool = False
+from .inria import GaussianRasterizationSettings as SurfelRasterizationSettings, _check_inputs      # (upstream's 12 fields, the same tuple)
 
 
 class _SurfelRasterizeFn(torch.autograd.Function):
@@ -112,8 +96,7 @@ class SurfelGaussianRasterizer(torch.nn.Module):
         self.raster_settings = raster_settings
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None):
-        if (shs is None) == (colors_precomp is None):
-            raise Exception("Please provide excatly one of either SHs or precomputed colors!")
+        _check_inputs(shs, colors_precomp)
         if cov3D_precomp is not None:
             raise NotImplementedError("precomputed transforms (cov3D_precomp) are not supported by the HIP surfel rasterizer; pass scales "
                                       "and rotations")

@@ -8,7 +8,6 @@ internal/models/vanilla_gaussian.py:266-300) through the same kernel.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from typing import Optional
 

@@ -11,12 +11,12 @@ Differences that are deliberate:
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Tuple
 
 import torch
 
 from .. import ops
-from .renderer import Renderer, RendererOutputInfo, RendererOutputTypes, camera_hw, viewspace_grad_scale, implementation_tile_size, model_sh_pair
+from .renderer import Renderer, RenderTypes, camera_hw, viewspace_grad_scale, implementation_tile_size, model_sh_pair
 
 DEFAULT_BLOCK_SIZE: int = 16
 DEFAULT_ANTI_ALIASED_STATUS: bool = True
@@ -48,29 +48,7 @@ def _project(means3D, scales, rotations, viewpoint_camera, scaling_modifier, blo
         img_height=H, img_width=W, block_width=block_size, filter_2d_kernel_size=kernel_size, return_cov3d=False, **extra)
 
 
-class HipGSplatRenderer(Renderer):
-    _RGB_REQUIRED = 1
-    _ALPHA_REQUIRED = 1 << 1
-    _ACC_DEPTH_REQUIRED = 1 << 2
-    _ACC_DEPTH_INVERTED_REQUIRED = 1 << 3
-    _EXP_DEPTH_REQUIRED = 1 << 4
-    _EXP_DEPTH_INVERTED_REQUIRED = 1 << 5
-    _INVERSE_DEPTH_REQUIRED = 1 << 6
-    _HARD_DEPTH_REQUIRED = 1 << 7
-    _HARD_INVERSE_DEPTH_REQUIRED = 1 << 8
-
-    RENDER_TYPE_BITS = {
-        "rgb": _RGB_REQUIRED,
-        "alpha": _ALPHA_REQUIRED | _ACC_DEPTH_REQUIRED,
-        "acc_depth": _ACC_DEPTH_REQUIRED,
-        "acc_depth_inverted": _ACC_DEPTH_REQUIRED | _ACC_DEPTH_INVERTED_REQUIRED,
-        "exp_depth": _ACC_DEPTH_REQUIRED | _EXP_DEPTH_REQUIRED,
-        "exp_depth_inverted": _ACC_DEPTH_REQUIRED | _EXP_DEPTH_REQUIRED | _EXP_DEPTH_INVERTED_REQUIRED,
-        "inverse_depth": _INVERSE_DEPTH_REQUIRED,
-        "hard_depth": _HARD_DEPTH_REQUIRED,
-        "hard_inverse_depth": _HARD_INVERSE_DEPTH_REQUIRED,
-    }
-
+class HipGSplatRenderer(RenderTypes, Renderer):
     def __init__(self, block_size: int = DEFAULT_BLOCK_SIZE, anti_aliased: bool = DEFAULT_ANTI_ALIASED_STATUS,
                  kernel_size: float = 0.3, absgrad: bool = False) -> None:
         super().__init__()
@@ -78,18 +56,6 @@ class HipGSplatRenderer(Renderer):
         self.anti_aliased = anti_aliased
         self.filter_2d_kernel_size = kernel_size
         self.absgrad = absgrad
-
-    def parse_render_types(self, render_types: list) -> int:
-        if render_types is None:
-            return self._RGB_REQUIRED
-        bits = 0
-        for i in render_types:
-            bits |= self.RENDER_TYPE_BITS[i]
-        return bits
-
-    @staticmethod
-    def is_type_required(bits: int, type: int) -> bool:
-        return bits & type != 0
 
     def forward(self, viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, render_types: list = None, **kwargs):
         bits = self.parse_render_types(render_types)
@@ -221,17 +187,3 @@ class HipGSplatRenderer(Renderer):
         return {"render": rgb.permute(2, 0, 1), "viewspace_points": xys,
                 "viewspace_points_grad_scale": viewspace_grad_scale(W, H, xys),
                 "visibility_filter": radii > 0, "radii": radii}
-
-    def get_available_outputs(self) -> Dict:
-        g = RendererOutputTypes.GRAY
-        return {
-            "rgb": RendererOutputInfo("render"),
-            "alpha": RendererOutputInfo("alpha", type=g),
-            "acc_depth": RendererOutputInfo("acc_depth", type=g),
-            "acc_depth_inverted": RendererOutputInfo("acc_depth_inverted", type=g),
-            "exp_depth": RendererOutputInfo("exp_depth", type=g),
-            "exp_depth_inverted": RendererOutputInfo("exp_depth_inverted", type=g),
-            "inverse_depth": RendererOutputInfo("inverse_depth", type=g),
-            "hard_depth": RendererOutputInfo("hard_depth", type=g),
-            "hard_inverse_depth": RendererOutputInfo("hard_inverse_depth", type=g),
-        }

@@ -15,7 +15,7 @@ from typing import Any, Tuple
 import torch
 
 from .. import ops
-from .renderer import Renderer, RendererConfig, RendererOutputInfo, RendererOutputTypes, camera_hw, implementation_tile_size
+from .renderer import Renderer, RendererConfig, RendererOutputInfo, RendererOutputTypes, RenderTypes, camera_hw, implementation_tile_size
 
 
 @dataclass
@@ -46,32 +46,11 @@ def build_rotation_col2(q: torch.Tensor) -> torch.Tensor:
     return torch.stack([2 * (x * z + w * y), 2 * (y * z - w * x), 1 - 2 * (x * x + y * y)], dim=-1)
 
 
-class HipGSplatV1RendererModule(Renderer):
-    _RGB_REQUIRED = 1
-    _ALPHA_REQUIRED = 1 << 1
-    _ACC_DEPTH_REQUIRED = 1 << 2
-    _ACC_DEPTH_INVERTED_REQUIRED = 1 << 3
-    _EXP_DEPTH_REQUIRED = 1 << 4
-    _EXP_DEPTH_INVERTED_REQUIRED = 1 << 5
-    _INVERSE_DEPTH_REQUIRED = 1 << 6
-    _HARD_DEPTH_REQUIRED = 1 << 7
-    _HARD_INVERSE_DEPTH_REQUIRED = 1 << 8
+class HipGSplatV1RendererModule(RenderTypes, Renderer):
     _DEPTH_ALTERNATIVE = 1 << 9
     _NORMAL_REQUIRED = 1 << 10
 
-    RENDER_TYPE_BITS = {
-        "rgb": _RGB_REQUIRED,
-        "alpha": _ALPHA_REQUIRED | _ACC_DEPTH_REQUIRED,
-        "acc_depth": _ACC_DEPTH_REQUIRED,
-        "acc_depth_inverted": _ACC_DEPTH_REQUIRED | _ACC_DEPTH_INVERTED_REQUIRED,
-        "exp_depth": _ACC_DEPTH_REQUIRED | _EXP_DEPTH_REQUIRED,
-        "exp_depth_inverted": _ACC_DEPTH_REQUIRED | _EXP_DEPTH_REQUIRED | _EXP_DEPTH_INVERTED_REQUIRED,
-        "inverse_depth": _INVERSE_DEPTH_REQUIRED,
-        "hard_depth": _HARD_DEPTH_REQUIRED,
-        "hard_inverse_depth": _HARD_INVERSE_DEPTH_REQUIRED,
-        "inv_depth_alt": _DEPTH_ALTERNATIVE,
-        "normal": _NORMAL_REQUIRED,
-    }
+    RENDER_TYPE_BITS = {**RenderTypes.RENDER_TYPE_BITS, "inv_depth_alt": _DEPTH_ALTERNATIVE, "normal": _NORMAL_REQUIRED}
 
     def __init__(self, config: HipGSplatV1Renderer):
         super().__init__()
@@ -87,19 +66,11 @@ class HipGSplatV1RendererModule(Renderer):
         self._inv_depth_alt = [self.RENDER_TYPE_BITS["inverse_depth"], self.RENDER_TYPE_BITS["hard_inverse_depth"]]
 
     def parse_render_types(self, render_types: list) -> int:
-        if render_types is None:
-            return self._RGB_REQUIRED
-        bits = 0
-        for i in render_types:
-            bits |= self.RENDER_TYPE_BITS[i]
+        bits = super().parse_render_types(render_types)
         if self.is_type_required(bits, self._DEPTH_ALTERNATIVE):
             bits |= self._inv_depth_alt[self._inv_depth_alt_state]
             self._inv_depth_alt_state = int(not self._inv_depth_alt_state)
         return bits
-
-    @staticmethod
-    def is_type_required(bits: int, type: int) -> bool:
-        return bits & type != 0
 
     def get_scales(self, camera, gaussian_model, **kwargs) -> Tuple[torch.Tensor, Any]:
         return gaussian_model.get_scales(), None
@@ -239,18 +210,7 @@ class HipGSplatV1RendererModule(Renderer):
         self._viewer_options = (clip, model)
 
     def get_available_outputs(self):
-        g = RendererOutputTypes.GRAY
-        return {
-            "rgb": RendererOutputInfo("render"), "alpha": RendererOutputInfo("alpha", type=g),
-            "acc_depth": RendererOutputInfo("acc_depth", type=g),
-            "acc_depth_inverted": RendererOutputInfo("acc_depth_inverted", type=g),
-            "exp_depth": RendererOutputInfo("exp_depth", type=g),
-            "exp_depth_inverted": RendererOutputInfo("exp_depth_inverted", type=g),
-            "inverse_depth": RendererOutputInfo("inverse_depth", type=g),
-            "hard_depth": RendererOutputInfo("hard_depth", type=g),
-            "hard_inverse_depth": RendererOutputInfo("hard_inverse_depth", type=g),
-            "normal": RendererOutputInfo("normal", type=RendererOutputTypes.NORMAL_MAP),
-        }
+        return {**super().get_available_outputs(), "normal": RendererOutputInfo("normal", type=RendererOutputTypes.NORMAL_MAP)}
 
 
 class GSplatV1:

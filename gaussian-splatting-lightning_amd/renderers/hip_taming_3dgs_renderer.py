@@ -14,8 +14,8 @@ from typing import Dict
 import torch
 
 from .. import ops
-from .hip_vanilla_renderer import HipVanillaRenderer
-from .renderer import Renderer, RendererOutputInfo, RendererOutputTypes, model_raw_parameters, model_sh_pair
+from .renderer import (Renderer, RendererOutputInfo, RendererOutputTypes, model_sh_pair, model_geometry, raster_settings, screenspace_carrier,
+                       marked_visibility)
 
 
 class HipTaming3DGSRenderer(Renderer):
@@ -34,14 +34,9 @@ class HipTaming3DGSRenderer(Renderer):
             render_types = ["rgb"]
         want_invdepth = "inverse_depth" in render_types
         means3D = pc.get_xyz
-        screenspace_points = torch.empty_like(means3D, dtype=means3D.dtype, device=bg_color.device).requires_grad_(True)
-        settings = HipVanillaRenderer._settings(viewpoint_camera, bg_color, scaling_modifier, pc.active_sh_degree)
-
-        raw = model_raw_parameters(pc) if self.fuse_activations else None
-        if raw is not None:
-            scales, rotations, opacities = raw
-        else:
-            scales, rotations, opacities = pc.get_scaling, pc.get_rotation, pc.get_opacity
+        screenspace_points = screenspace_carrier(means3D, bg_color.device)
+        settings = raster_settings(viewpoint_camera, bg_color, scaling_modifier, pc.active_sh_degree)
+        scales, rotations, opacities, raw = model_geometry(pc, self.fuse_activations)
 
         shs = shs_rest = None
         colors_precomp = kwargs.get("colors_precomp", None)
@@ -50,14 +45,12 @@ class HipTaming3DGSRenderer(Renderer):
 
         rendered_image, radii, inverse_depth = ops.rasterize_inria_accel(
             settings, means3D, screenspace_points, opacities, shs, colors_precomp, scales, rotations, None, shs_rest=shs_rest,
-            raw_parameters=raw is not None, antialiasing=self.anti_aliased, inverse_depth=want_invdepth)
-        visibility_filter = radii > 0
-        visibility_filter._gspl_radii_positive = True      # density.HipDensityStatsMixin: the mask the fused backward applies itself
+            raw_parameters=raw, antialiasing=self.anti_aliased, inverse_depth=want_invdepth)
         return {
             "render": rendered_image,
             "inverse_depth": inverse_depth,
             "viewspace_points": screenspace_points,
-            "visibility_filter": visibility_filter,
+            "visibility_filter": marked_visibility(radii),
             "radii": radii,
         }
 

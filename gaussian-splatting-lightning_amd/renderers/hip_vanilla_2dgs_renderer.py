@@ -13,8 +13,7 @@ from typing import Dict
 import torch
 
 from .. import ops
-from .hip_vanilla_renderer import camera_hw, camera_scalars, _tan_half
-from .renderer import Renderer, RendererOutputInfo, RendererOutputTypes
+from .renderer import Renderer, RendererOutputInfo, RendererOutputTypes, camera_hw, raster_settings
 
 
 class HipVanilla2DGSRenderer(Renderer):
@@ -22,19 +21,11 @@ class HipVanilla2DGSRenderer(Renderer):
         super().__init__()
         self.depth_ratio = depth_ratio
 
-    @staticmethod
-    def _settings(viewpoint_camera, bg_color, scaling_modifier, sh_degree):
-        W, H = camera_hw(viewpoint_camera)
-        fov_x, fov_y = camera_scalars(viewpoint_camera, ("fov_x", "fov_y"))
-        return ops.SurfelRasterizationSettings(
-            image_height=H, image_width=W, tanfovx=_tan_half(fov_x), tanfovy=_tan_half(fov_y), bg=bg_color,
-            scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_to_camera, projmatrix=viewpoint_camera.full_projection,
-            sh_degree=int(sh_degree), campos=viewpoint_camera.camera_center, prefiltered=False, debug=False)
-
     def forward(self, viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, **kwargs):
         means3D = pc.get_xyz
         screenspace_points = torch.zeros_like(means3D, dtype=means3D.dtype, requires_grad=True, device=bg_color.device) + 0
-        rasterizer = ops.SurfelGaussianRasterizer(self._settings(viewpoint_camera, bg_color, scaling_modifier, pc.active_sh_degree))
+        rasterizer = ops.SurfelGaussianRasterizer(raster_settings(viewpoint_camera, bg_color, scaling_modifier, pc.active_sh_degree,
+                                                                  cls=ops.SurfelRasterizationSettings))
         colors_precomp = kwargs.get("colors_precomp", None)
         shs = pc.get_features if colors_precomp is None else None
         rendered_image, radii, allmap = rasterizer(means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,

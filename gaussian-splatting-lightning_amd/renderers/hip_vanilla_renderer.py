@@ -8,17 +8,13 @@ Output contract (vanilla_renderer.py:122-129): `render` [3,H,W], `viewspace_poin
 """
 from __future__ import annotations
 
-import math
 from typing import Dict, Optional
 
 import torch
 
 from .. import ops
-from .renderer import Renderer, RendererOutputInfo, RendererOutputTypes, camera_hw, camera_scalars, model_sh_pair, model_raw_parameters
-
-
-def _tan_half(fov):
-    return math.tan(float(fov) * 0.5)
+from .renderer import (Renderer, RendererOutputInfo, RendererOutputTypes, model_sh_pair, model_geometry, raster_settings, screenspace_carrier,
+                       marked_visibility)
 
 
 class HipVanillaRenderer(Renderer):
@@ -30,17 +26,6 @@ class HipVanillaRenderer(Renderer):
         self.compute_cov3D_python = compute_cov3D_python
         self.convert_SHs_python = convert_SHs_python
         self.fuse_activations = fuse_activations
-
-    @staticmethod
-    def _settings(viewpoint_camera, bg_color, scaling_modifier, sh_degree):
-        W, H = camera_hw(viewpoint_camera)
-        fov_x, fov_y = camera_scalars(viewpoint_camera, ("fov_x", "fov_y"))
-        return ops.GaussianRasterizationSettings(
-            image_height=H, image_width=W,
-            tanfovx=_tan_half(fov_x), tanfovy=_tan_half(fov_y),
-            bg=bg_color, scale_modifier=scaling_modifier,
-            viewmatrix=viewpoint_camera.world_to_camera, projmatrix=viewpoint_camera.full_projection,
-            sh_degree=int(sh_degree), campos=viewpoint_camera.camera_center, prefiltered=False, debug=False)
 
     def forward(self, viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
                 render_types: list = None, **kwargs):
@@ -57,23 +42,14 @@ class HipVanillaRenderer(Renderer):
             override_color = depth.repeat(1, 3)
 
         means3D = pc.get_xyz
-        # The screen-space tensor only CARRIES the 2D-mean gradient back to the density controller; its values are never read
-        # (reference: `zeros_like(...) + 0`, vanilla_renderer.py:55-56 — a fill and an add per frame).  A leaf accepts
-        # `retain_grad()` and receives `.grad` just the same.
-        screenspace_points = torch.empty_like(means3D, dtype=means3D.dtype, device=bg_color.device).requires_grad_(True)
-        settings = self._settings(viewpoint_camera, bg_color, scaling_modifier, pc.active_sh_degree)
-        rasterizer = ops.GaussianRasterizer(raster_settings=settings)
+        screenspace_points = screenspace_carrier(means3D, bg_color.device)
+        rasterizer = ops.GaussianRasterizer(raster_settings(viewpoint_camera, bg_color, scaling_modifier, pc.active_sh_degree))
 
-        scales = rotations = cov3D_precomp = opacities = None
-        raw = model_raw_parameters(pc) if (self.fuse_activations and not self.compute_cov3D_python) else None
         if self.compute_cov3D_python:
-            cov3D_precomp = pc.get_covariance(scaling_modifier)
-        elif raw is not None:
-            scales, rotations, opacities = raw
+            scales, rotations, cov3D_precomp, opacities, raw = None, None, pc.get_covariance(scaling_modifier), pc.get_opacity, False
         else:
-            scales, rotations = pc.get_scaling, pc.get_rotation
-        if opacities is None:
-            opacities = pc.get_opacity
+            cov3D_precomp = None
+            scales, rotations, opacities, raw = model_geometry(pc, self.fuse_activations)
 
         shs = shs_rest = colors_precomp = None
         if override_color is None:
@@ -92,13 +68,11 @@ class HipVanillaRenderer(Renderer):
         rendered_image, radii = rasterizer(
             means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp,
             opacities=opacities, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, shs_rest=shs_rest,
-            raw_parameters=raw is not None)
-        visibility_filter = radii > 0
-        visibility_filter._gspl_radii_positive = True      # density.HipDensityStatsMixin: the mask the fused backward applies itself
+            raw_parameters=raw)
         return {
             rendered_image_key: rendered_image,
             "viewspace_points": screenspace_points,
-            "visibility_filter": visibility_filter,
+            "visibility_filter": marked_visibility(radii),
             "radii": radii,
         }
 
@@ -110,15 +84,12 @@ class HipVanillaRenderer(Renderer):
             assert features is None
         if cov3D_precomp is not None:
             assert scales is None and rotations is None
-        screenspace_points = torch.empty_like(means3D, dtype=means3D.dtype, device=means3D.device).requires_grad_(True)
-        settings = HipVanillaRenderer._settings(viewpoint_camera, bg_color, scaling_modifier, active_sh_degree)
-        rendered_image, radii = ops.GaussianRasterizer(raster_settings=settings)(
+        screenspace_points = screenspace_carrier(means3D, means3D.device)
+        rendered_image, radii = ops.GaussianRasterizer(raster_settings(viewpoint_camera, bg_color, scaling_modifier, active_sh_degree))(
             means3D=means3D, means2D=screenspace_points, shs=features, colors_precomp=colors_precomp,
             opacities=opacity, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
-        visibility_filter = radii > 0
-        visibility_filter._gspl_radii_positive = True
         return {"render": rendered_image, "depth": None, "viewspace_points": screenspace_points,
-                "visibility_filter": visibility_filter, "radii": radii}
+                "visibility_filter": marked_visibility(radii), "radii": radii}
 
     def get_available_outputs(self) -> Dict:
         return {"rgb": RendererOutputInfo("render"), "depth": RendererOutputInfo("depth", RendererOutputTypes.GRAY)}

@@ -7,10 +7,13 @@ reference's own (`internal/renderers/renderer.py:43-117`), so `isinstance(render
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Any, Callable, Dict
 
 import torch
+
+from .. import ops
 
 try:  # pragma: no cover - only inside the reference repo
     from internal.renderers.renderer import (  # type: ignore
@@ -116,6 +119,30 @@ def camera_hw(viewpoint_camera):
     return int(w), int(h)
 
 
+def raster_settings(viewpoint_camera, bg_color, scaling_modifier, sh_degree, cls=ops.GaussianRasterizationSettings):
+    """The camera as upstream's 12 rasterization settings, in `cls` (the Inria tuple, or a stand-in package's own)."""
+    W, H = camera_hw(viewpoint_camera)
+    fov_x, fov_y = camera_scalars(viewpoint_camera, ("fov_x", "fov_y"))
+    return cls(
+        image_height=H, image_width=W, tanfovx=math.tan(float(fov_x) * 0.5), tanfovy=math.tan(float(fov_y) * 0.5), bg=bg_color,
+        scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_to_camera, projmatrix=viewpoint_camera.full_projection,
+        sh_degree=int(sh_degree), campos=viewpoint_camera.camera_center, prefiltered=False, debug=False)
+
+
+def screenspace_carrier(means3D, device):
+    """The screen-space tensor only CARRIES the 2D-mean gradient back to the density controller; its values are never read
+    (reference: `zeros_like(...) + 0`, vanilla_renderer.py:55-56 — a fill and an add per frame).  A leaf accepts `retain_grad()`
+    and receives `.grad` just the same."""
+    return torch.empty_like(means3D, dtype=means3D.dtype, device=device).requires_grad_(True)
+
+
+def marked_visibility(radii):
+    """`radii > 0`, marked as such: density.HipDensityStatsMixin then knows it is the mask the fused backward applies itself."""
+    visibility_filter = radii > 0
+    visibility_filter._gspl_radii_positive = True
+    return visibility_filter
+
+
 _GRAD_SCALES: dict = {}
 
 
@@ -143,7 +170,6 @@ def model_sh_pair(pc):
             pass
     # `get_features` reads the parameters through torch (a cat, or the stored tensor of a pre-activated model): an update of the
     # coefficients still in flight on the colour stream (FusedAdam(deferred=...)) has to land first
-    from .. import ops
     ops.join_pending_updates(pc.get_xyz.device)
     return pc.get_features, None
 
@@ -190,6 +216,61 @@ def model_raw_parameters(pc):
         return pc.get_property("scales"), pc.get_property("rotations"), pc.get_property("opacities")
     except (KeyError, AttributeError):
         return None
+
+
+def model_geometry(pc, fuse_activations: bool):
+    """(scales, rotations, opacities, raw): the model's RAW parameters (`model_raw_parameters`, raw = True) when `fuse_activations`
+    allows and the model qualifies, else what its getters return."""
+    raw = model_raw_parameters(pc) if fuse_activations else None
+    if raw is not None:
+        return (*raw, True)
+    return pc.get_scaling, pc.get_rotation, pc.get_opacity, False
+
+
+class RenderTypes:
+    """The render types of the reference's two gsplat renderers (gsplat_renderer.py:13-47, gsplat_v1_renderer.py:52-98) as bits, for
+    both plugins (mixed in before `Renderer`); the class attributes are the reference's, which other renderers of it read."""
+    _RGB_REQUIRED = 1
+    _ALPHA_REQUIRED = 1 << 1
+    _ACC_DEPTH_REQUIRED = 1 << 2
+    _ACC_DEPTH_INVERTED_REQUIRED = 1 << 3
+    _EXP_DEPTH_REQUIRED = 1 << 4
+    _EXP_DEPTH_INVERTED_REQUIRED = 1 << 5
+    _INVERSE_DEPTH_REQUIRED = 1 << 6
+    _HARD_DEPTH_REQUIRED = 1 << 7
+    _HARD_INVERSE_DEPTH_REQUIRED = 1 << 8
+
+    RENDER_TYPE_BITS = {
+        "rgb": _RGB_REQUIRED,
+        "alpha": _ALPHA_REQUIRED | _ACC_DEPTH_REQUIRED,
+        "acc_depth": _ACC_DEPTH_REQUIRED,
+        "acc_depth_inverted": _ACC_DEPTH_REQUIRED | _ACC_DEPTH_INVERTED_REQUIRED,
+        "exp_depth": _ACC_DEPTH_REQUIRED | _EXP_DEPTH_REQUIRED,
+        "exp_depth_inverted": _ACC_DEPTH_REQUIRED | _EXP_DEPTH_REQUIRED | _EXP_DEPTH_INVERTED_REQUIRED,
+        "inverse_depth": _INVERSE_DEPTH_REQUIRED,
+        "hard_depth": _HARD_DEPTH_REQUIRED,
+        "hard_inverse_depth": _HARD_INVERSE_DEPTH_REQUIRED,
+    }
+
+    def parse_render_types(self, render_types: list) -> int:
+        if render_types is None:
+            return self._RGB_REQUIRED
+        bits = 0
+        for i in render_types:
+            bits |= self.RENDER_TYPE_BITS[i]
+        return bits
+
+    @staticmethod
+    def is_type_required(bits: int, type: int) -> bool:
+        return bits & type != 0
+
+    def get_available_outputs(self) -> Dict[str, RendererOutputInfo]:
+        """"rgb" and every other common type as a gray image under its own name."""
+        outputs = {"rgb": RendererOutputInfo("render")}
+        for name in RenderTypes.RENDER_TYPE_BITS:
+            if name != "rgb":
+                outputs[name] = RendererOutputInfo(name, type=RendererOutputTypes.GRAY)
+        return outputs
 
 
 _TILE_NOTE = set()

@@ -14,17 +14,12 @@ sum chains.
 Prints one JSON line.  `--slice-only K` runs K slice forward + backward pairs at 1080p and a TV forward + backward at N = 300, and
 nothing else (for `rocprofv3 --kernel-trace --stats`).
   python tools/bilagrid_step_time.py [--rounds 5] [--steps 20] [--warmup 5]"""
-import argparse
 import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import torch
+import torch.nn.functional as F
 
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
+import _step_time as T
 
 GRAY = (0.299, 0.587, 0.114)
 N_GRIDS = 300
@@ -68,27 +63,9 @@ SLICE = {"torch": torch_slice, "hip": hip_slice}
 TV = {"torch": torch_tv, "hip": hip_tv}
 
 
-def _timed(fn, steps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(steps):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / steps
-
-
 def _alternate(fn, rounds, steps, warmup):
-    times = {"torch": [], "hip": []}
-    for r in range(rounds):
-        for v in (("torch", "hip") if r % 2 == 0 else ("hip", "torch")):
-            times[v].append(_timed(lambda: fn(v), steps, warmup))
-    med = {v: statistics.median(times[v]) for v in times}
-    return {"ms_median": {v: round(med[v], 4) for v in med}, "ms_rounds": {v: [round(x, 4) for x in times[v]] for v in times},
-            "speedup": round(med["torch"] / med["hip"], 2)}
+    med, med_print, rounds_print = T.medians(T.alternate(("torch", "hip"), lambda v, _i: fn(v), rounds, steps, warmup))
+    return {"ms_median": med_print, "ms_rounds": rounds_print, "speedup": round(med["torch"] / med["hip"], 2)}
 
 
 def _grids(n, dev, seed=0):
@@ -98,12 +75,8 @@ def _grids(n, dev, seed=0):
 
 
 def main():
-    p = argparse.ArgumentParser()
-    p.add_argument("--rounds", type=int, default=5)
-    p.add_argument("--steps", type=int, default=20)
-    p.add_argument("--warmup", type=int, default=5)
+    p = T.arguments(steps=20, warmup=5, workload="S-1080p-1M")
     p.add_argument("--slice-only", type=int, default=0)
-    p.add_argument("--workload", default="S-1080p-1M")
     a = p.parse_args()
     import gspl_amd  # noqa: F401
     assert torch.cuda.is_available(), "bilagrid_step_time measures on the GPU"
@@ -150,20 +123,14 @@ def main():
 
     # (iii) the training step with and without the processor
     import bench_loop
-    from gspl_amd import ops, optimizers, synthetic
-    wl = synthetic.WORKLOADS[a.workload]
-    Wi, Hi = wl["width"], wl["height"]
-    cams = synthetic.camera_set(Wi, Hi, wl["fx"], count=16, distance=wl.get("distance", 4.0))
-    cams = [{k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in c.items()} for c in cams]
-    bg = torch.zeros(3, device=dev)
-    target = torch.rand(3, Hi, Wi, device=dev, generator=torch.Generator(device=dev).manual_seed(7))
-    order = [int(i) for i in synthetic.epoch_order(len(cams), 0)]
+    from gspl_amd import ops, optimizers
+    w = T.load(a.workload, dev)
+    wl, Wi, Hi, cams, order, bg, target = w.wl, w.W, w.H, w.cams, w.order, w.bg, w.target
     gy, gx = torch.meshgrid(torch.linspace(0, 1, Hi, device=dev), torch.linspace(0, 1, Wi, device=dev), indexing="ij")
     xy_w = torch.stack([gx, gy], dim=-1).unsqueeze(0)
 
     def model_for():
-        means, scales, quats, opac, shs = [t.to(dev) for t in synthetic.workload_scene(wl, seed=42)]
-        return bench_loop.RawGaussians(means, scales, quats, opac, shs, active_sh_degree=3)
+        return bench_loop.RawGaussians(*T.scene(wl, dev), active_sh_degree=3)
     variants = ("plain", "torch", "hip")
     models = {v: model_for() for v in variants}
     opts = {v: models[v].make_optimizers(1.0, optimizers.FusedAdam) for v in variants}
@@ -196,13 +163,8 @@ def main():
             gopt[v].step()
             gopt[v].zero_grad(set_to_none=True)
 
-    times = {v: [] for v in variants}
-    for r in range(a.rounds):
-        for v in (variants if r % 2 == 0 else variants[::-1]):
-            times[v].append(_timed(lambda: step(v), a.steps, a.warmup))
-    med = {v: statistics.median(times[v]) for v in variants}
-    result["training_step"] = {"workload": a.workload, "n_grids": N_GRIDS, "ms_median": {v: round(med[v], 4) for v in variants},
-                               "ms_rounds": {v: [round(x, 4) for x in times[v]] for v in variants},
+    med, med_print, rounds_print = T.medians(T.alternate(variants, lambda v, _i: step(v), a.rounds, a.steps, a.warmup))
+    result["training_step"] = {"workload": a.workload, "n_grids": N_GRIDS, "ms_median": med_print, "ms_rounds": rounds_print,
                                "processor_cost_ms": {v: round(med[v] - med["plain"], 4) for v in ("torch", "hip")}}
     print(json.dumps(result))
 

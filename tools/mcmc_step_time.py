@@ -15,18 +15,12 @@ by round inside ONE process so that clock and thermal drift spread over both.
 Prints one JSON line.  `--noise-only K` runs K noise launches and nothing else (for `rocprofv3 --kernel-trace --stats`), and prints the
 bytes the kernel must move: 56 B per Gaussian (means read + written, scales, rotations, opacity).
   python tools/mcmc_step_time.py [--workloads S-1080p-1M,S-1080p-6M] [--rounds 5] [--steps 20] [--warmup 5]"""
-import argparse
 import json
-import math
-import os
-import statistics
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import torch
 
-import torch  # noqa: E402
+import _step_time as T
 
 NOISE_LR, MEANS_LR, REG_W = 5e5, 1.6e-4, 0.01
 BYTES_PER_GAUSSIAN = 56
@@ -78,25 +72,9 @@ def hip_reg(g):
     return o + s
 
 
-def _timed(fn, steps, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    t0.record()
-    for _ in range(steps):
-        fn()
-    t1.record()
-    torch.cuda.synchronize()
-    return t0.elapsed_time(t1) / steps
-
-
 def main():
-    p = argparse.ArgumentParser()
+    p = T.arguments(steps=20, warmup=5)
     p.add_argument("--workloads", default="S-1080p-1M,S-1080p-6M")
-    p.add_argument("--rounds", type=int, default=5)
-    p.add_argument("--steps", type=int, default=20)
-    p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--noise-only", type=int, default=0)
     a = p.parse_args()
     import gspl_amd  # noqa: F401
@@ -109,8 +87,7 @@ def main():
     result = {"tool": "mcmc_step_time", "rounds": a.rounds, "steps": a.steps, "warmup": a.warmup, "bytes_per_gaussian_noise": BYTES_PER_GAUSSIAN}
 
     def model_for(wl):
-        means, scales, quats, opac, shs = [t.to(dev) for t in synthetic.workload_scene(wl, seed=42)]
-        return bench_loop.RawGaussians(means, scales, quats, opac, shs, active_sh_degree=3)
+        return bench_loop.RawGaussians(*T.scene(wl, dev), active_sh_degree=3)
 
     workloads = [w for w in a.workloads.split(",") if w]
     if a.noise_only:
@@ -125,13 +102,8 @@ def main():
         return
 
     for wname in workloads:
-        wl = synthetic.WORKLOADS[wname]
-        W, H = wl["width"], wl["height"]
-        cams = synthetic.camera_set(W, H, wl["fx"], count=16, distance=wl.get("distance", 4.0))
-        cams = [{k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in c.items()} for c in cams]
-        bg = torch.zeros(3, device=dev)
-        target = torch.rand(3, H, W, device=dev, generator=torch.Generator(device=dev).manual_seed(7))
-        order = [int(i) for i in synthetic.epoch_order(len(cams), 0)]
+        w = T.load(wname, dev)
+        wl, W, H, cams, order, bg, target = w.wl, w.W, w.H, w.cams, w.order, w.bg, w.target
         models = {v: model_for(wl) for v in ("torch", "hip")}
         opts = {v: models[v].make_optimizers(1.0, optimizers.FusedAdam) for v in models}
         reg = {"torch": torch_reg, "hip": hip_reg}
@@ -166,13 +138,8 @@ def main():
 
         rec = {}
         for name, fn in (("step", step), ("noise", noise_alone), ("regulariser", reg_alone)):
-            times = {"torch": [], "hip": []}
-            for r in range(a.rounds):
-                for v in (("torch", "hip") if r % 2 == 0 else ("hip", "torch")):
-                    times[v].append(_timed(lambda: fn(v), a.steps, a.warmup))
-            med = {v: statistics.median(times[v]) for v in times}
-            rec[name] = {"ms_median": {v: round(med[v], 4) for v in med}, "ms_rounds": {v: [round(x, 4) for x in times[v]] for v in times},
-                         "saving_ms": round(med["torch"] - med["hip"], 4)}
+            med, med_print, rounds_print = T.medians(T.alternate(("torch", "hip"), lambda v, _i: fn(v), a.rounds, a.steps, a.warmup))
+            rec[name] = {"ms_median": med_print, "ms_rounds": rounds_print, "saving_ms": round(med["torch"] - med["hip"], 4)}
         rec["noise"]["hip_achieved_GBps_from_event_time"] = round(BYTES_PER_GAUSSIAN * wl["n"] / (rec["noise"]["ms_median"]["hip"] * 1e-3) / 1e9, 1)
         result[wname] = {"n": wl["n"], **rec}
         del models, opts

@@ -9,16 +9,9 @@ both:
 Prints one JSON line: per variant the median over rounds of the mean step time (ms) and the surfel / vanilla ratio.
   python tools/surfel_step_time.py [--workload S-1080p-1M] [--rounds 5] [--steps 30] [--warmup 8] [--variants vanilla,surfel]
 Under `rocprofv3 --kernel-trace --stats -- python tools/surfel_step_time.py --variants surfel --rounds 1` it gives per-kernel figures."""
-import argparse
-import json
-import os
-import statistics
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import torch  # noqa: E402
+import _step_time as T
 
 VARIANTS = ("vanilla", "surfel")
 
@@ -50,28 +43,16 @@ class _SurfelModel:
 
 
 def main():
-    p = argparse.ArgumentParser()
-    p.add_argument("--workload", default="S-1080p-1M")
-    p.add_argument("--rounds", type=int, default=5)
-    p.add_argument("--steps", type=int, default=30)
-    p.add_argument("--warmup", type=int, default=8)
-    p.add_argument("--variants", default=",".join(VARIANTS))
-    a = p.parse_args()
+    a = T.arguments(steps=30, warmup=8, workload="S-1080p-1M", variants=VARIANTS).parse_args()
     import gspl_amd  # noqa: F401
-    from gspl_amd import ops, optimizers, synthetic
+    from gspl_amd import ops, optimizers
     from gspl_amd.renderers import HipVanilla2DGSRenderer
-    variants = [v for v in a.variants.split(",") if v]
-    assert all(v in VARIANTS for v in variants), variants
+    variants = T.chosen_variants(a, VARIANTS)
     dev = torch.device("cuda:0")
-    wl = synthetic.WORKLOADS[a.workload]
-    W, H = wl["width"], wl["height"]
-    means, scales, quats, opac, shs = [t.to(dev) for t in synthetic.workload_scene(wl, seed=42)]
-    cams = synthetic.camera_set(W, H, wl["fx"], count=16, distance=wl.get("distance", 4.0))
-    cams = [{k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in c.items()} for c in cams]
+    w = T.load(a.workload, dev)
+    W, H, cams, order, bg, target = w.W, w.H, w.cams, w.order, w.bg, w.target
+    means, scales, quats, opac, shs = T.scene(w.wl, dev)
     rcams = [_Camera(c, dev) for c in cams]
-    bg = torch.zeros(3, device=dev)
-    gen = torch.Generator(device=dev).manual_seed(7)
-    target = torch.rand(3, H, W, device=dev, generator=gen)
     renderer = HipVanilla2DGSRenderer(depth_ratio=0.0)
 
     def make(variant):
@@ -83,7 +64,9 @@ def main():
         groups = [{"params": [q], "name": str(i)} for i, q in enumerate(params)]
         return params, optimizers.FusedAdam(groups, lr=1e-4)
 
-    def step(variant, params, opt, ci):
+    def step(variant, i):
+        params, opt = state[variant]
+        ci = order[i % len(order)]
         cam = cams[ci]
         if variant == "vanilla":
             m, s, q, o, dc, rest = params
@@ -103,28 +86,9 @@ def main():
         opt.zero_grad(set_to_none=True)
 
     state = {v: make(v) for v in variants}
-    order = [int(i) for i in synthetic.epoch_order(len(cams), 0)]
-    times = {v: [] for v in variants}
-    k = 0
-    for r in range(a.rounds):
-        for v in (variants if r % 2 == 0 else variants[::-1]):
-            params, opt = state[v]
-            for i in range(a.warmup):
-                step(v, params, opt, order[(k + i) % len(order)])
-            torch.cuda.synchronize()
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-            for i in range(a.steps):
-                step(v, params, opt, order[(k + i) % len(order)])
-            t1.record()
-            torch.cuda.synchronize()
-            times[v].append(t0.elapsed_time(t1) / a.steps)
-        k += a.steps
-    med = {v: statistics.median(times[v]) for v in variants}
-    print(json.dumps({"workload": a.workload, "cameras": "heterogeneous x16", "rounds": a.rounds, "steps": a.steps,
-                      "ms_per_step_median": {v: round(med[v], 4) for v in variants},
-                      "ms_per_step_rounds": {v: [round(x, 4) for x in times[v]] for v in variants},
-                      "ratio_surfel_to_vanilla": (round(med["surfel"] / med["vanilla"], 4) if len(med) == 2 else None)}))
+    times = T.alternate(variants, step, a.rounds, a.steps, a.warmup)
+    T.print_step_times(a, times, lambda med: {
+        "ratio_surfel_to_vanilla": (round(med["surfel"] / med["vanilla"], 4) if len(med) == 2 else None)})
 
 
 if __name__ == "__main__":
