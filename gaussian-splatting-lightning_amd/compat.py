@@ -9,8 +9,10 @@ pypreprocess_gsplat_renderer.py:1-2, gsplat_hit_pixel_count_renderer.py:5, inter
 op of `gspl_amd.ops` with the same signature.  With them the reference's OWN renderer classes (`VanillaRenderer`,
 `GSPlatRenderer`, `GSplatV1Renderer`, the research renderers built on their static helpers) run unedited on the HIP kernels; the
 `Hip*` plugins of `gspl_amd.renderers` remain the faster route (fused calls, list-only binning, channels-first images).
-Functions of the fork that are not built (`compute_relocation`, `depth_to_normal`, `rasterize_to_vis_aware_weights`) are left
-out: importing them raises ImportError as it would without the package.
+`gsplat.utils.depth_to_normal` (internal/metrics/normal_reg.py:3) is served by `ops.depth_to_normal` with the semantics of the
+published gsplat `utils.py`; parity with the fork's own build of it is unpinned (there is no ROCm build to compare against).
+Functions of the fork that are not built (`compute_relocation`, `rasterize_to_vis_aware_weights`) are left out: importing them
+raises ImportError as it would without the package.
 
 The reference imports them by their own module names inside functions, e.g.
 `from simple_knn._C import distCUDA2` (internal/models/vanilla_gaussian.py:122) or `from fused_ssim import fused_ssim`
@@ -77,6 +79,27 @@ def _rasterize_to_pixels_fork(*args, **kwargs):
     return ops.rasterize_to_pixels(*args, **kwargs)
 
 
+def _depth_to_normal(depths, camtoworlds, Ks, z_depth=True):
+    """gsplat's `utils.depth_to_normal` as published: depths [..., H, W, 1], camtoworlds [..., 4, 4], Ks [..., 3, 3] -> normals
+    [..., H, W, 3] in world space, zero on the one-pixel border.  Pixel centres lie at +0.5 (`ops.gsplat_rays`); z_depth=False means
+    `depths` are distances along the normalised rays.  One `ops.depth_to_normal` launch per image, A built on the device without a
+    read-back; the gradient reaches `depths` only.  Parity with the yzslab fork's build is unpinned: these are the published
+    semantics, which the reference's call site (internal/metrics/normal_reg.py:29-33) relies on."""
+    import torch
+    from . import ops
+    if depths.dim() < 3 or depths.shape[-1] != 1:
+        raise ValueError(f"depths must be [..., H, W, 1], got {tuple(depths.shape)}")
+    H, W = int(depths.shape[-3]), int(depths.shape[-2])
+    lead = tuple(depths.shape[:-3])
+    d = depths.reshape(-1, H, W)
+    c2w = camtoworlds.expand(*lead, 4, 4).reshape(-1, 4, 4)
+    Ks = Ks.expand(*lead, 3, 3).reshape(-1, 3, 3)
+    if d.shape[0] == 0:
+        return depths.new_zeros((*lead, H, W, 3))
+    maps = [ops.depth_to_normal(d[i], ops.gsplat_rays(c2w[i], Ks[i]).to(d.dtype), normalize_rays=not z_depth) for i in range(d.shape[0])]
+    return torch.stack(maps).reshape(*lead, H, W, 3)
+
+
 def _module(name: str, doc: str, **attrs):
     mod = types.ModuleType(name)
     mod.__doc__ = doc
@@ -127,6 +150,7 @@ def _install_rasterizer_packages(installed: list):
             isect_offset_encode_tile_based_culling=_isect_offset_encode_tile_based_culling)
         pkg.hit_pixel_count = _module("gsplat.hit_pixel_count", doc, hit_pixel_count=_late("hit_pixel_count"))
         pkg.rasterize_to_weights = _module("gsplat.rasterize_to_weights", doc, rasterize_to_weights=_late("rasterize_to_weights"))
+        pkg.utils = _module("gsplat.utils", doc, depth_to_normal=_depth_to_normal)
         from . import optimizers
         pkg.optimizers = _module("gsplat.optimizers", doc, SelectiveAdam=optimizers.SelectiveAdam)
         installed.append("gsplat")

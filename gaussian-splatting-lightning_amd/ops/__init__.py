@@ -15,6 +15,8 @@ reference's renderers call (same names, argument meaning and error behaviour):
       compute_relocation, perturb_means_, mcmc_regularization
   Bilateral grid (internal/output_processors/bilagrid.py, `fused_bilagrid`; the module-level API is gspl_amd.bilagrid)
       bilagrid_slice, bilagrid_tv
+  Surface maps (internal/renderers/vanilla_2dgs_renderer.py:146-170, internal/metrics/gs2d_metrics.py, `gsplat.utils.depth_to_normal`)
+      depth_to_normal, gsplat_rays, surfel_maps, surface_reg
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -43,6 +45,7 @@ from .inria import (GaussianRasterizationSettings, GaussianRasterizer, _InriaRas
 from .surfel import SurfelRasterizationSettings, SurfelGaussianRasterizer, rasterize_surfels, _SurfelRasterizeFn
 from .mcmc import compute_relocation, perturb_means_, mcmc_regularization, mcmc_randn, _MCMCRegFn
 from .bilagrid import bilagrid_slice, bilagrid_tv, _SliceFn, _TvFn
+from .surface import depth_to_normal, gsplat_rays, surfel_maps, surface_reg, _DepthNormalFn, _SurfelMapsFn, _SurfaceRegFn
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

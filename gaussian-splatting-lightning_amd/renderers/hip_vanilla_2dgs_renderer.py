@@ -4,7 +4,10 @@ by the HIP surfel rasterizer of ops/surfel.py instead of `diff_surfel_rasterizat
 Select with   --model.renderer gspl_amd.renderers.HipVanilla2DGSRenderer   (`--model.renderer.depth_ratio 1` for bounded
 scenes, as the reference's option).  Outputs and `get_available_outputs` are the reference's: `render`, `viewspace_points` (its `.grad`
 receives the 2DGS densification proxy), `visibility_filter`, `radii`, `rend_alpha`, `rend_normal` (world space), `view_normal`,
-`rend_dist`, `surf_depth`, `surf_normal`.  The pseudo surface normal from the depth map stays in torch, on the camera's device.
+`rend_dist`, `surf_depth`, `surf_normal`.  By default the pseudo surface normal from the depth map stays in torch, on the camera's
+device; with `--model.renderer.fused_maps true` everything after the rasterizer call is ONE HIP launch per direction
+(`ops.surfel_maps`, csrc/normals.hip) with the camera's two 3x3 matrices kept on the camera object.  One difference of that route:
+where alpha is 0 the gradient of the depth and alpha planes is 0 instead of the torch formulation's NaN.
 """
 from __future__ import annotations
 
@@ -17,9 +20,10 @@ from .renderer import Renderer, RendererOutputInfo, RendererOutputTypes, camera_
 
 
 class HipVanilla2DGSRenderer(Renderer):
-    def __init__(self, depth_ratio: float = 0.):
+    def __init__(self, depth_ratio: float = 0., fused_maps: bool = False):
         super().__init__()
         self.depth_ratio = depth_ratio
+        self.fused_maps = fused_maps
 
     def forward(self, viewpoint_camera, pc, bg_color: torch.Tensor, scaling_modifier=1.0, **kwargs):
         means3D = pc.get_xyz
@@ -32,6 +36,19 @@ class HipVanilla2DGSRenderer(Renderer):
                                                    opacities=pc.get_opacity, scales=pc.get_scaling[..., :2], rotations=pc.get_rotation,
                                                    cov3D_precomp=None)
         rets = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
+
+        if self.fused_maps:
+            normal_rot, rays = self.camera_matrices(viewpoint_camera, allmap)
+            render_normal, surf_depth, surf_normal = ops.surfel_maps(allmap, normal_rot, rays, self.depth_ratio)
+            rets.update({
+                "rend_alpha": allmap[1:2],
+                "rend_normal": render_normal,
+                "view_normal": -allmap[2:5],
+                "rend_dist": allmap[6:7],
+                "surf_depth": surf_depth,
+                "surf_normal": surf_normal,
+            })
+            return rets
 
         render_alpha = allmap[1:2]
         w2c3 = viewpoint_camera.world_to_camera[:3, :3].to(allmap.dtype)
@@ -51,6 +68,36 @@ class HipVanilla2DGSRenderer(Renderer):
             "surf_normal": surf_normal,
         })
         return rets
+
+    @classmethod
+    def camera_matrices(cls, view, like):
+        """(normal_rot, rays) of `ops.surfel_maps` for a camera, [3, 3] each on `like`'s device: the view-to-world rotation of the
+        normal planes and the matrix that takes (x, y, 1) to the pixel's ray, built with the torch expressions of `forward` and
+        `depths_to_points` (no read-back) and kept on the camera object — dataset cameras persist across steps, so a step adds no
+        matrix launches.  Keyed on identity and version counter of the two source tensors, as `GSplatV1.preprocess_camera`.  The op
+        treats both as constants: the fused route passes no gradient to a camera pose."""
+        dev, dt = like.device, like.dtype
+        src = (view.world_to_camera, view.full_projection)
+        cacheable = all(isinstance(v, torch.Tensor) and not v.requires_grad for v in src)
+        if cacheable:
+            key = tuple((id(v), v._version) for v in src) + camera_hw(view) + (str(dev), dt)
+            hit = getattr(view, "_gspl_surfel_matrices", None)
+            if hit is not None and hit[0] == key and all(a is b for a, b in zip(hit[1], src)):
+                return hit[2], hit[3]
+        w2c = view.world_to_camera.to(device=dev, dtype=dt)
+        normal_rot = w2c[:3, :3].contiguous()
+        c2w = w2c.T.inverse()
+        W, H = camera_hw(view)
+        ndc2pix = torch.tensor([[W / 2, 0, 0, W / 2], [0, H / 2, 0, H / 2], [0, 0, 0, 1]], dtype=dt, device=dev).T
+        projection_matrix = c2w.T @ view.full_projection.to(device=dev, dtype=dt)
+        intrins = (projection_matrix @ ndc2pix)[:3, :3].T
+        rays = (c2w[:3, :3] @ intrins.inverse()).contiguous()
+        if cacheable:
+            try:
+                view._gspl_surfel_matrices = (key, src, normal_rot, rays)
+            except AttributeError:
+                pass
+        return normal_rot, rays
 
     @staticmethod
     def depths_to_points(view, depthmap):

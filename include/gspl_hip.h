@@ -826,6 +826,54 @@ int gspl_bilagrid_tv_partials(int64_t n);
 int gspl_bilagrid_tv_fwd(int N, int C, int L, int GH, int GW, const float* x, float* partials, float* out, void* stream);
 int gspl_bilagrid_tv_bwd(int N, int C, int L, int GH, int GW, const float* x, const float* grad_out, float* grad_x, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 15. Normal maps from depth maps, the 2DGS maps and the surface regulariser sums (csrc/normals.hip).  PURELY ADDITIVE: seven new
+ *    entry points, nothing existing changes, GSPL_ABI_VERSION stays 39.  fp32, device pointers only, no float atomics; every element
+ *    of every output is written (hand over uninitialised memory); results are bit-reproducible.
+ *
+ *  The stencil.  rays [3,3] row-major (DEVICE memory) is a matrix A; r(y,x) = A (x, y, 1)^T, with normalize_rays r / max(|r|, 1e-12);
+ *  q(y,x) = depth(y,x) r(y,x) (the camera origin cancels below and is left out).  For an interior pixel
+ *        dx = q(y+1,x) - q(y-1,x),  dy = q(y,x+1) - q(y,x-1),  c = dx x dy,  n = c / max(|c|, 1e-12)        (F.normalize's rule)
+ *  and n = 0 on the one-pixel border; H < 3 or W < 3 gives all zeros.  This is the 2DGS renderer's `depth_to_normal` (A = c2w[:3,:3]
+ *  intrins^-1) and, with A = c2w[:3,:3] [[1/fx, 0, (0.5 - cx)/fx], [0, 1/fy, (0.5 - cy)/fy], [0, 0, 1]], gsplat's `utils.depth_to_normal`
+ *  (normalize_rays = not z_depth).
+ *  gspl_depth_normal_fwd: depth [H,W] -> normal, 3 H W floats in `layout` (GSPL_LAYOUT_HWC: [H,W,3], GSPL_LAYOUT_CHW: [3,H,W]).
+ *  gspl_depth_normal_bwd: v_normal (in `layout`) -> v_depth [H,W], a gather: each pixel adds up, in a fixed order, what the four centres
+ *      (y+-1,x), (y,x+-1) that read it contribute, recomputing their cross products from `depth` (a radius-2 diamond).  Where
+ *      |c| <= 1e-12 the constant denominator is kept, v_c = v_n / 1e-12, as torch's F.normalize backward does: gradients there carry
+ *      that 1e12 scale (and are exactly 0 where the depth map is exactly 0 around the pixel).
+ *  gspl_surfel_maps_fwd: allmap [7,H,W] (planes: depth | alpha | view normal x3 | median depth | distortion), normal_rot [3,3] and
+ *      rays [3,3] (device), rho = depth_ratio:
+ *        rend_normal [3,H,W] = normal_rot allmap[2:5]
+ *        surf_depth  [1,H,W] = (1 - rho) nan0(allmap0 / alpha) + rho nan0(allmap5),   nan0 = torch.nan_to_num(x, 0, 0): NaN, +inf -> 0,
+ *                              -inf -> the lowest finite value
+ *        surf_normal [3,H,W] = stencil(surf_depth) alpha                                (alpha is a constant of this product)
+ *  gspl_surfel_maps_bwd: the three upstream gradients (each nullable = zero) -> v_allmap [7,H,W], written completely: plane 6 is 0;
+ *      planes 2..4 = normal_rot^T v_rend_normal; with v = v_surf_depth + the stencil's gather, plane 0 = v (1 - rho) / alpha, plane 1 =
+ *      -v (1 - rho) allmap0 / alpha^2 (from the expected depth only), plane 5 = v rho.  Planes 0 and 1 are 0 where allmap0 / alpha is
+ *      not finite, plane 5 where allmap5 is not: nan0 passes no gradient there.  (torch's formulation leaves NaN in planes 0 and 1 at
+ *      alpha = 0, from 0 / 0 in the division's backward; that is deliberately not reproduced.)
+ *  gspl_surface_reg_fwd: a, b [3,H,W], dist [H,W] (nullable): out[0] = mean_p (1 - sum_c a_c b_c), out[1] = mean_p dist (0 without
+ *      dist).  Deterministic: gspl_surface_reg_partials(H W) workgroups write 2 partial sums each to `partials` (2x as many floats),
+ *      one workgroup adds them in a fixed order.  A thread adds at most 64 terms serially, a workgroup's tree is 9 additions deep,
+ *      at both levels; 1 <= H W <= 2^28.
+ *  gspl_surface_reg_bwd: grad_out [2] on the device -> v_a = -grad_out[0] b / (H W), v_b = -grad_out[0] a / (H W), v_dist =
+ *      grad_out[1] / (H W); each output nullable (not written).
+ * ---------------------------------------------------------------------------------------- */
+int gspl_depth_normal_fwd(int H, int W, const float* depth, const float* rays, int normalize_rays, int layout, float* normal, void* stream);
+int gspl_depth_normal_bwd(int H, int W, const float* depth, const float* rays, int normalize_rays, const float* v_normal, int layout,
+                          float* v_depth, void* stream);
+int gspl_surfel_maps_fwd(int H, int W, const float* allmap, const float* normal_rot, const float* rays, float depth_ratio,
+                         float* rend_normal, float* surf_depth, float* surf_normal, void* stream);
+int gspl_surfel_maps_bwd(int H, int W, const float* allmap, const float* normal_rot, const float* rays, float depth_ratio,
+                         const float* v_rend_normal /*nullable*/, const float* v_surf_depth /*nullable*/,
+                         const float* v_surf_normal /*nullable*/, float* v_allmap, void* stream);
+int gspl_surface_reg_partials(int64_t n);
+int gspl_surface_reg_fwd(int H, int W, const float* a, const float* b, const float* dist /*nullable*/, float* partials, float* out,
+                         void* stream);
+int gspl_surface_reg_bwd(int H, int W, const float* a, const float* b, const float* grad_out, float* v_a /*nullable*/,
+                         float* v_b /*nullable*/, float* v_dist /*nullable*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

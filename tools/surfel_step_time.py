@@ -5,15 +5,18 @@ both:
   vanilla   GaussianRasterizer (raw parameters, shs / shs_rest) + FusedAdam, the L1 + SSIM loss
   surfel    HipVanilla2DGSRenderer forward, the L1 + SSIM loss plus GS2D's normal-consistency and distortion terms, backward, and Adam
             (FusedAdam over the activated parameters: the 2DGS renderer takes the model's activated values)
+  surfel-fused  the same step with `HipVanilla2DGSRenderer(fused_maps=True)` (everything after the rasterizer is `ops.surfel_maps`) and
+            the two regularisers from one `ops.surface_reg` call (csrc/normals.hip)
 
-Prints one JSON line: per variant the median over rounds of the mean step time (ms) and the surfel / vanilla ratio.
+Prints one JSON line: per variant the median over rounds of the mean step time (ms), the surfel / vanilla and the surfel-fused / surfel
+ratios where both were run.
   python tools/surfel_step_time.py [--workload S-1080p-1M] [--rounds 5] [--steps 30] [--warmup 8] [--variants vanilla,surfel]
 Under `rocprofv3 --kernel-trace --stats -- python tools/surfel_step_time.py --variants surfel --rounds 1` it gives per-kernel figures."""
 import torch
 
 import _step_time as T
 
-VARIANTS = ("vanilla", "surfel")
+VARIANTS = ("vanilla", "surfel", "surfel-fused")
 
 
 class _Camera:
@@ -43,7 +46,7 @@ class _SurfelModel:
 
 
 def main():
-    a = T.arguments(steps=30, warmup=8, workload="S-1080p-1M", variants=VARIANTS).parse_args()
+    a = T.arguments(steps=30, warmup=8, workload="S-1080p-1M", variants=VARIANTS[:2]).parse_args()
     import gspl_amd  # noqa: F401
     from gspl_amd import ops, optimizers
     from gspl_amd.renderers import HipVanilla2DGSRenderer
@@ -54,6 +57,7 @@ def main():
     means, scales, quats, opac, shs = T.scene(w.wl, dev)
     rcams = [_Camera(c, dev) for c in cams]
     renderer = HipVanilla2DGSRenderer(depth_ratio=0.0)
+    fused_renderer = HipVanilla2DGSRenderer(depth_ratio=0.0, fused_maps=True)
 
     def make(variant):
         if variant == "vanilla":
@@ -76,6 +80,11 @@ def main():
             img, _ = ops.GaussianRasterizer(st)(m, screen, o, shs=dc, shs_rest=rest, scales=s, rotations=q, raw_parameters=True)
             l1, ssim = ops.l1_ssim(img, target)
             loss = 0.8 * l1 + 0.2 * (1 - ssim)
+        elif variant == "surfel-fused":
+            out = fused_renderer(rcams[ci], _SurfelModel(params), bg)
+            l1, ssim = ops.l1_ssim(out["render"], target)
+            reg = ops.surface_reg(out["rend_normal"], out["surf_normal"], out["rend_dist"])
+            loss = 0.8 * l1 + 0.2 * (1 - ssim) + 0.05 * reg[0] + 100.0 * reg[1]
         else:
             out = renderer(rcams[ci], _SurfelModel(params), bg)
             l1, ssim = ops.l1_ssim(out["render"], target)
@@ -87,8 +96,9 @@ def main():
 
     state = {v: make(v) for v in variants}
     times = T.alternate(variants, step, a.rounds, a.steps, a.warmup)
-    T.print_step_times(a, times, lambda med: {
-        "ratio_surfel_to_vanilla": (round(med["surfel"] / med["vanilla"], 4) if len(med) == 2 else None)})
+    ratio = lambda med, x, y: round(med[x] / med[y], 4) if x in med and y in med else None
+    T.print_step_times(a, times, lambda med: {"ratio_surfel_to_vanilla": ratio(med, "surfel", "vanilla"),
+                                              "ratio_fused_to_surfel": ratio(med, "surfel-fused", "surfel")})
 
 
 if __name__ == "__main__":
