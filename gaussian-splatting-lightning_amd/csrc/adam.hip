@@ -35,12 +35,11 @@ __global__ __launch_bounds__(256) void selective_adam_kernel(AdamBatchDev batch,
     const int64_t total = (int64_t)N * T.row;
     const float step = T.lr * inv_bc1;
     const int64_t nvec = total >> 2;
-#ifndef GSPL_ADAM_V1
     typedef float v4f __attribute__((ext_vector_type(4)));
     auto ntl = [](const float* base, int64_t i) { const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(base) + i); return make_float4(t.x, t.y, t.z, t.w); };
     auto nts = [](float* base, int64_t i, const float4& q) { v4f t = {q.x, q.y, q.z, q.w}; __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(base) + i); };
     // two 16-byte chunks per thread and iteration (8 loads in flight) and streaming (nontemporal) accesses of everything that is
-    // not read again before the next step: 302 -> 257 us at 1 M Gaussians (1.65 GB: 6.4 TB/s); -DGSPL_ADAM_V1 = the one-chunk loop
+    // not read again before the next step: 302 -> 257 us at 1 M Gaussians (1.65 GB: 6.4 TB/s)
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < nvec; i0 += 2 * stride) {
         float4 p[2], g[2], m[2], v[2];
@@ -73,27 +72,6 @@ __global__ __launch_bounds__(256) void selective_adam_kernel(AdamBatchDev batch,
             nts(T.v, i, v[u]);
         }
     }
-#else
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t e = i << 2;
-        bool vis[4];
-        bool any = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { vis[k] = visible ? visible[(e + k) / T.row] != 0 : true; any = any || vis[k]; }
-        if (!any) continue;
-        float4 p = reinterpret_cast<float4*>(T.p)[i];
-        const float4 g = reinterpret_cast<const float4*>(T.g)[i];
-        float4 m = reinterpret_cast<float4*>(T.m)[i];
-        float4 v = reinterpret_cast<float4*>(T.v)[i];
-        if (vis[0]) adam_elem(p.x, g.x, m.x, v.x, step, b1, b2, inv_bc2, eps);
-        if (vis[1]) adam_elem(p.y, g.y, m.y, v.y, step, b1, b2, inv_bc2, eps);
-        if (vis[2]) adam_elem(p.z, g.z, m.z, v.z, step, b1, b2, inv_bc2, eps);
-        if (vis[3]) adam_elem(p.w, g.w, m.w, v.w, step, b1, b2, inv_bc2, eps);
-        reinterpret_cast<float4*>(T.p)[i] = p;
-        reinterpret_cast<float4*>(T.m)[i] = m;
-        reinterpret_cast<float4*>(T.v)[i] = v;
-    }
-#endif
     // tail (total not a multiple of 4)
     if (blockIdx.x == 0) {
         for (int64_t e = (nvec << 2) + threadIdx.x; e < total; e += blockDim.x) {

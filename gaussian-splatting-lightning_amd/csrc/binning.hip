@@ -517,20 +517,18 @@ extern "C" size_t gspl_bin_workspace_bytes(int N, int64_t n_isects) {
 
 namespace gspl {
 // gspl_bin_count; ticket != 0: host_counts has a third word that receives the ticket AFTER the two numbers (the caller polls it)
-int bin_count_ticket(int N, int mode, const float* means2d, const int32_t* radii, const float* depths,
-                              const float* conics, const float* opacities,
-                              int tile_size, int tile_w, int tile_h,
-                              int32_t* order, int64_t* cum_tiles, int32_t* big_list, void* spans, int64_t* host_counts,
-                              void* workspace, size_t workspace_bytes, void* stream, unsigned long long ticket,
-                              bool depth_header_zeroed, ZeroJob then_zero) {
-    if (N < 0 || tile_size <= 0 || tile_w <= 0 || tile_h <= 0) return fail_arg("bin_count: bad sizes");
-    if (mode != GSPL_MODE_GSPLAT && mode != GSPL_MODE_INRIA) return fail_arg("bin_count: bad mode");
+int bin_count_ticket(const BinSplats& in, TileGrid grid, const BinOrder& ord, int64_t* host_counts,
+                     void* workspace, size_t workspace_bytes, void* stream, unsigned long long ticket,
+                     bool depth_header_zeroed, ZeroJob then_zero) {
+    const int N = in.N;
+    if (N < 0 || grid.size <= 0 || grid.w <= 0 || grid.h <= 0) return fail_arg("bin_count: bad sizes");
+    if (in.mode != GSPL_MODE_GSPLAT && in.mode != GSPL_MODE_INRIA) return fail_arg("bin_count: bad mode");
     if (N == 0) return GSPL_OK;
-    if (!means2d || !radii || !depths || !order || !cum_tiles || !big_list || !spans || !workspace) return fail_arg("bin_count: NULL required pointer");
-    if (tile_w > 65535 || tile_h > 65535) { set_error("bin_count", "more than 65535 tile rows or columns"); return GSPL_ERR_UNSUPPORTED; }
-    if ((conics == nullptr) != (opacities == nullptr)) return fail_arg("bin_count: conics and opacities go together");
+    if (!in.means2d || !in.radii || !in.depths || !ord.order || !ord.cum || !ord.big_list || !ord.spans || !workspace) return fail_arg("bin_count: NULL required pointer");
+    if (grid.w > 65535 || grid.h > 65535) { set_error("bin_count", "more than 65535 tile rows or columns"); return GSPL_ERR_UNSUPPORTED; }
+    if ((in.conics == nullptr) != (in.opacities == nullptr)) return fail_arg("bin_count: conics and opacities go together");
     BinWorkspace w;
-    int rc = plan_bin(N, 0, tile_w * tile_h, w);
+    int rc = plan_bin(N, 0, grid.n(), w);
     if (rc != GSPL_OK) return rc;
     if (workspace_bytes < w.total_count) return fail_ws("bin_count");
     static_assert(GSPL_BIN_SPAN_BYTES == 2 * sizeof(SpanRecord), "spans = N primary + N extension records");
@@ -540,7 +538,7 @@ int bin_count_ticket(int N, int mode, const float* means2d, const int32_t* radii
     uint32_t* keys2 = (uint32_t*)(ws + w.keys2_off);
     int32_t* counts = (int32_t*)(ws + w.counts_off);
     hipStream_t s = (hipStream_t)stream;
-    const int grid = (N + 255) / 256;
+    const int blocks = (N + 255) / 256;
     // Depth sort (sort.hip), prepared by the key pass itself (the first pass's counts).  Four 8-bit passes: the sorted sequence
     // ends where it started, so the key pass writes the ids straight into `order`.
     const RadixPlan& dp = w.depth;
@@ -550,20 +548,20 @@ int bin_count_ticket(int N, int mode, const float* means2d, const int32_t* radii
         rc = radix_zero(ws + w.sort1_off, dp.header_bytes, s);
         if (rc != GSPL_OK) return rc;
     }
-    if (mode == GSPL_MODE_GSPLAT)
-        hipLaunchKernelGGL((bin_keys_kernel<GSPL_MODE_GSPLAT, true>), dim3(grid), dim3(256), 0, s, N, means2d, radii, depths, conics, opacities, tile_size, tile_w, tile_h, keys, (uint32_t*)order, counts, (SpanRecord*)spans, hdr);
-    else
-        hipLaunchKernelGGL((bin_keys_kernel<GSPL_MODE_INRIA, true>), dim3(grid), dim3(256), 0, s, N, means2d, radii, depths, conics, opacities, tile_size, tile_w, tile_h, keys, (uint32_t*)order, counts, (SpanRecord*)spans, hdr);
+    dispatch_mode(in.mode, [&](auto m) {
+        hipLaunchKernelGGL((bin_keys_kernel<m(), true>), dim3(blocks), dim3(256), 0, s, N, in.means2d, in.radii, in.depths, in.conics, in.opacities,
+                           grid.size, grid.w, grid.h, keys, (uint32_t*)ord.order, counts, (SpanRecord*)ord.spans, hdr);
+    });
     rc = check_launch("bin_keys");
     if (rc != GSPL_OK) return rc;
     uint32_t* const kbuf[2] = {keys, keys2};
-    uint32_t* const vbuf[2] = {(uint32_t*)order, ids};
+    uint32_t* const vbuf[2] = {(uint32_t*)ord.order, ids};
     // the last pass leaves the tile counts in depth order where the sorted keys would go
     rc = radix_sort_u32(dp, ws + w.sort1_off, kbuf, vbuf, true, s, (const uint32_t*)counts);
     if (rc != GSPL_OK) return rc;
     // the scan also ranks the tagged (big) splats: big_list[rank] = depth index, cum_tiles[N] = how many — one 16-byte read-back
     // gives the host both numbers
-    return scan_gathered_counts(nullptr, (const int32_t*)kbuf[dp.passes & 1], cum_tiles, (size_t)N, ws + w.sort1_off + w.scan_states_off, big_list, s, host_counts,
+    return scan_gathered_counts(nullptr, (const int32_t*)kbuf[dp.passes & 1], ord.cum, (size_t)N, ws + w.sort1_off + w.scan_states_off, ord.big_list, s, host_counts,
                                 host_counts ? ticket : 0ull, then_zero);
 }
 
@@ -591,8 +589,9 @@ extern "C" int gspl_bin_count(int N, int mode, const float* means2d, const int32
                               int tile_size, int tile_w, int tile_h,
                               int32_t* order, int64_t* cum_tiles, int32_t* big_list, void* spans, int64_t* host_counts,
                               void* workspace, size_t workspace_bytes, void* stream) {
-    return gspl::bin_count_ticket(N, mode, means2d, radii, depths, conics, opacities, tile_size, tile_w, tile_h, order, cum_tiles, big_list, spans, host_counts,
-                                  workspace, workspace_bytes, stream, 0ull);
+    using namespace gspl;
+    return bin_count_ticket(BinSplats{N, mode, means2d, radii, depths, conics, opacities}, TileGrid{tile_size, tile_w, tile_h},
+                            BinOrder{order, cum_tiles, big_list, spans}, host_counts, workspace, workspace_bytes, stream, 0ull);
 }
 
 // Emission half of gspl_bin_emit_sort.  `capacity` = records the workspace (gspl_bin_workspace_bytes(N, capacity)) has
@@ -604,28 +603,29 @@ extern "C" int gspl_bin_emit(int N, int mode, const float* means2d, const int32_
                              const int32_t* order, const int64_t* cum_tiles, const int32_t* big_list, const void* spans,
                              int tile_size, int tile_w, int tile_h, int64_t capacity,
                              void* workspace, size_t workspace_bytes, void* stream) {
-    return gspl::bin_emit_impl(N, mode, means2d, radii, conics, opacities, order, cum_tiles, big_list, spans, tile_size, tile_w, tile_h, capacity,
-                               workspace, workspace_bytes, stream, false);
+    using namespace gspl;      // (BinOrder is also what the count half writes: the emission only reads it)
+    return bin_emit_impl(BinSplats{N, mode, means2d, radii, nullptr, conics, opacities},
+                         BinOrder{const_cast<int32_t*>(order), const_cast<int64_t*>(cum_tiles), const_cast<int32_t*>(big_list), const_cast<void*>(spans)},
+                         TileGrid{tile_size, tile_w, tile_h}, capacity, workspace, workspace_bytes, stream, false);
 }
 
 namespace gspl {
-int bin_emit_impl(int N, int mode, const float* means2d, const int32_t* radii, const float* conics, const float* opacities,
-                  const int32_t* order, const int64_t* cum_tiles, const int32_t* big_list, const void* spans,
-                  int tile_size, int tile_w, int tile_h, int64_t capacity, void* workspace, size_t workspace_bytes, void* stream,
+int bin_emit_impl(const BinSplats& in, const BinOrder& ord, TileGrid grid, int64_t capacity, void* workspace, size_t workspace_bytes, void* stream,
                   bool tile_header_zeroed) {
-    if (N < 0 || capacity < 0 || tile_size <= 0 || tile_w <= 0 || tile_h <= 0) return fail_arg("bin_emit: bad sizes");
-    if (mode != GSPL_MODE_GSPLAT && mode != GSPL_MODE_INRIA) return fail_arg("bin_emit: bad mode");
+    const int N = in.N;
+    if (N < 0 || capacity < 0 || grid.size <= 0 || grid.w <= 0 || grid.h <= 0) return fail_arg("bin_emit: bad sizes");
+    if (in.mode != GSPL_MODE_GSPLAT && in.mode != GSPL_MODE_INRIA) return fail_arg("bin_emit: bad mode");
     if (N == 0 || capacity == 0) return GSPL_OK;
     if (capacity > 0x7fffffffll) return fail_arg("bin_emit: more than 2^31-1 intersections");
-    if (!means2d || !radii || !order || !cum_tiles || !big_list || !spans || !workspace) return fail_arg("bin_emit: NULL required pointer");
+    if (!in.means2d || !in.radii || !ord.order || !ord.cum || !ord.big_list || !ord.spans || !workspace) return fail_arg("bin_emit: NULL required pointer");
     BinWorkspace w;
-    int rc = plan_bin(N, capacity, tile_w * tile_h, w);
+    int rc = plan_bin(N, capacity, grid.n(), w);
     if (rc != GSPL_OK) return rc;
     if (workspace_bytes < w.total) return fail_ws("bin_emit");
     char* ws = (char*)workspace;
     uint64_t* tkeys = (uint64_t*)(ws + w.tkeys_off);
     hipStream_t s = (hipStream_t)stream;
-    const int grid = (N + 255) / 256;
+    const int blocks = (N + 255) / 256;
     // the tile sort's first-pass counts: exactly the records written, by the spans of the plan for `capacity` records (the real
     // list is not longer, else the emission is repeated; gspl_bin_sort keeps the spans)
     RadixProducer hdr;
@@ -634,10 +634,10 @@ int bin_emit_impl(int N, int mode, const float* means2d, const int32_t* radii, c
         rc = radix_zero(ws + w.sort2_off, w.tile.header_bytes, s);
         if (rc != GSPL_OK) return rc;
     }
-    if (mode == GSPL_MODE_GSPLAT)
-        hipLaunchKernelGGL(bin_emit_lb_kernel<GSPL_MODE_GSPLAT>, dim3(grid), dim3(256), 0, s, N, means2d, radii, (const uint32_t*)order, conics, opacities, cum_tiles, (const SpanRecord*)spans, big_list, tile_size, tile_w, tile_h, tkeys, capacity, hdr);
-    else
-        hipLaunchKernelGGL(bin_emit_lb_kernel<GSPL_MODE_INRIA>, dim3(grid), dim3(256), 0, s, N, means2d, radii, (const uint32_t*)order, conics, opacities, cum_tiles, (const SpanRecord*)spans, big_list, tile_size, tile_w, tile_h, tkeys, capacity, hdr);
+    dispatch_mode(in.mode, [&](auto m) {
+        hipLaunchKernelGGL(bin_emit_lb_kernel<m()>, dim3(blocks), dim3(256), 0, s, N, in.means2d, in.radii, (const uint32_t*)ord.order, in.conics, in.opacities,
+                           (const int64_t*)ord.cum, (const SpanRecord*)ord.spans, (const int32_t*)ord.big_list, grid.size, grid.w, grid.h, tkeys, capacity, hdr);
+    });
     return check_launch("bin_emit");
 }
 }  // namespace gspl
@@ -708,26 +708,24 @@ extern "C" int gspl_bin_emit_sort(int N, int mode, const float* means2d, const i
     return gspl_bin_sort(N, tile_w, tile_h, n_isects, n_isects, flatten_ids, offsets, workspace, workspace_bytes, stream);
 }
 
-int gspl::bin_lists_known(int N, int mode, const float* means2d, const int32_t* radii, const float* conics, const float* opacities,
-                          const int32_t* order, const int64_t* cum_tiles, const int32_t* big_list, const void* spans,
-                          int tile_size, int tile_w, int tile_h, int64_t n_isects, gspl_alloc_fn alloc, void* alloc_ctx,
+int gspl::bin_lists_known(const BinSplats& in, const BinOrder& ord, TileGrid grid, int64_t n_isects, gspl_alloc_fn alloc, void* alloc_ctx,
                           int32_t** flatten_ids, int32_t* offsets, void* stream, const char* who) {
+    const int N = in.N;
     *flatten_ids = nullptr;
     if (n_isects > (int64_t)((1u << 30) - 1u)) {
         set_error(who, "more than 2^30-1 (tile, Gaussian) intersections in one frame: the per-tile lists hold at most 1073741823 entries");
         return GSPL_ERR_UNSUPPORTED;
     }
-    if (N <= 0 || n_isects <= 0) return gspl_bin_sort(0, tile_w, tile_h, 0, 0, nullptr, offsets, nullptr, 0, stream);      // (zeros)
+    if (N <= 0 || n_isects <= 0) return gspl_bin_sort(0, grid.w, grid.h, 0, 0, nullptr, offsets, nullptr, 0, stream);      // (zeros)
     const size_t ws_bytes = gspl_bin_workspace_bytes(N, n_isects);
     auto no_block = [&]() { set_error(who, "allocation call-back returned NULL: invalid argument"); return GSPL_ERR_INVALID_ARG; };
     void* ws = alloc(alloc_ctx, GSPL_BUF_LISTS_WORK, ws_bytes);
     if (!ws) return no_block();
-    const int rc = gspl_bin_emit(N, mode, means2d, radii, conics, opacities, order, cum_tiles, big_list, spans, tile_size, tile_w, tile_h, n_isects,
-                                 ws, ws_bytes, stream);
+    const int rc = bin_emit_impl(in, ord, grid, n_isects, ws, ws_bytes, stream, false);
     if (rc != GSPL_OK) return rc;
     *flatten_ids = (int32_t*)alloc(alloc_ctx, GSPL_BUF_LISTS, 4 * (size_t)n_isects);
     if (!*flatten_ids) return no_block();
-    return gspl_bin_sort(N, tile_w, tile_h, n_isects, n_isects, *flatten_ids, offsets, ws, ws_bytes, stream);
+    return gspl_bin_sort(N, grid.w, grid.h, n_isects, n_isects, *flatten_ids, offsets, ws, ws_bytes, stream);
 }
 
 extern "C" size_t gspl_isect_workspace_bytes(int N, int64_t n_isects) {
@@ -753,10 +751,9 @@ extern "C" int gspl_isect_count(int N, int mode, const float* means2d, const int
     int32_t* counts = (int32_t*)(ws + w.counts_off);
     const int grid = (N + 255) / 256;
     hipStream_t s = (hipStream_t)stream;
-    if (mode == GSPL_MODE_GSPLAT)
-        hipLaunchKernelGGL(isect_count_kernel<GSPL_MODE_GSPLAT>, dim3(grid), dim3(256), 0, s, N, means2d, radii, tile_size, tile_w, tile_h, tiles_per_gauss, counts);
-    else
-        hipLaunchKernelGGL(isect_count_kernel<GSPL_MODE_INRIA>, dim3(grid), dim3(256), 0, s, N, means2d, radii, tile_size, tile_w, tile_h, tiles_per_gauss, counts);
+    dispatch_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL(isect_count_kernel<m()>, dim3(grid), dim3(256), 0, s, N, means2d, radii, tile_size, tile_w, tile_h, tiles_per_gauss, counts);
+    });
     rc = check_launch("isect_count");
     if (rc != GSPL_OK) return rc;
     // inclusive scan of the counts in memory order: the scan of sort.hip with the identity gather
@@ -797,10 +794,9 @@ extern "C" int gspl_isect_emit_sort(int N, int mode, const float* means2d, const
     uint32_t* v0 = start_in_user ? uvals : wvals;
     uint64_t* k1 = start_in_user ? wkeys : ukeys;
     uint32_t* v1 = start_in_user ? wvals : uvals;
-    if (mode == GSPL_MODE_GSPLAT)
-        hipLaunchKernelGGL(isect_emit_kernel<GSPL_MODE_GSPLAT>, dim3(grid), dim3(256), 0, s, N, means2d, radii, depths, cum_tiles, tile_size, tile_w, tile_h, k0, v0);
-    else
-        hipLaunchKernelGGL(isect_emit_kernel<GSPL_MODE_INRIA>, dim3(grid), dim3(256), 0, s, N, means2d, radii, depths, cum_tiles, tile_size, tile_w, tile_h, k0, v0);
+    dispatch_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL(isect_emit_kernel<m()>, dim3(grid), dim3(256), 0, s, N, means2d, radii, depths, cum_tiles, tile_size, tile_w, tile_h, k0, v0);
+    });
     rc = check_launch("isect_emit");
     if (rc != GSPL_OK) return rc;
     uint64_t* kb[2] = {k0, k1};

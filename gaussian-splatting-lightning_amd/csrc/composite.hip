@@ -204,23 +204,18 @@ __global__ __launch_bounds__(64) void composite_fwd_kernel(
 }
 
 template <int D, int MODE, bool CHW>
-static int launch_fwd(int n_tiles, int tile_w, int width, int height, int64_t n_isects,
-                      const float* means2d, const float* conics, const float* colors, const float* opacities,
-                      const float* backgrounds, const int32_t* offsets, const int32_t* flatten_ids,
+static int launch_fwd(int n_tiles, int tile_w, ImageSize image, const CompositeSplats& sp, const TileLists& lists,
                       float* out_colors, float* out_alphas, float* final_Ts, int32_t* last_ids, uint8_t* hit_flags, hipStream_t s, ListTiles lt,
                       const SegState* seg_in) {
     SegState seg = {};
     // checkpoints: 16-pixel list tiles, three channels (or four in the Inria mode, with the 4th channel's array)
     if (seg_in && lt.log2 == 4 && (D == 3 || (D == 4 && MODE == GSPL_MODE_INRIA && (!seg_in->ckpt || seg_in->ckpt_x)))) seg = *seg_in;
     else if (seg_in) { seg.zero_p = seg_in->zero_p; seg.zero_n16 = seg_in->zero_n16; }
-    if (hit_flags)
-        hipLaunchKernelGGL((composite_fwd_kernel<D, MODE, CHW, true>), dim3(4 * n_tiles), dim3(64), 0, s,
-                           n_tiles, tile_w, width, height, n_isects, means2d, conics, colors, opacities, backgrounds,
-                           offsets, flatten_ids, out_colors, out_alphas, final_Ts, last_ids, hit_flags, lt, seg);
-    else
-        hipLaunchKernelGGL((composite_fwd_kernel<D, MODE, CHW, false>), dim3(4 * n_tiles), dim3(64), 0, s,
-                           n_tiles, tile_w, width, height, n_isects, means2d, conics, colors, opacities, backgrounds,
-                           offsets, flatten_ids, out_colors, out_alphas, final_Ts, last_ids, hit_flags, lt, seg);
+    dispatch_bools([&](auto hits) {
+        hipLaunchKernelGGL((composite_fwd_kernel<D, MODE, CHW, hits()>), dim3(4 * n_tiles), dim3(64), 0, s,
+                           n_tiles, tile_w, image.width, image.height, lists.n_isects, sp.means2d, sp.conics, sp.colors, sp.opacities, sp.backgrounds,
+                           lists.offsets, lists.flatten_ids, out_colors, out_alphas, final_Ts, last_ids, hit_flags, lt, seg);
+    }, hit_flags != nullptr);
     return check_launch("composite_fwd");
 }
 
@@ -311,11 +306,10 @@ __global__ __launch_bounds__(64) void composite_scores_kernel(
     }
 }
 
-int check_composite_args(int N, int64_t n_isects, int D, int mode, int layout, int width, int height,
-                        int tile_size, int tile_w, int tile_h, const char* who) {
-    if (N < 0 || n_isects < -1 || width <= 0 || height <= 0) return fail_arg(who);
-    if (tile_size != 8 && tile_size != 16 && tile_size != 32) { set_error(who, "tile_size must be 8, 16 or 32"); return GSPL_ERR_UNSUPPORTED; }
-    if (tile_w != (width + tile_size - 1) / tile_size || tile_h != (height + tile_size - 1) / tile_size) return fail_arg(who);
+int check_composite_args(int N, int64_t n_isects, int D, int mode, int layout, ImageSize image, TileGrid grid, const char* who) {
+    if (N < 0 || n_isects < -1 || image.width <= 0 || image.height <= 0) return fail_arg(who);
+    if (grid.size != 8 && grid.size != 16 && grid.size != 32) { set_error(who, "tile_size must be 8, 16 or 32"); return GSPL_ERR_UNSUPPORTED; }
+    if (grid.w != (image.width + grid.size - 1) / grid.size || grid.h != (image.height + grid.size - 1) / grid.size) return fail_arg(who);
     if (mode != GSPL_MODE_GSPLAT && mode != GSPL_MODE_INRIA) return fail_arg(who);
     if (layout != GSPL_LAYOUT_HWC && layout != GSPL_LAYOUT_CHW) return fail_arg(who);
     if (!(D == 1 || D == 2 || D == 3 || D == 4 || D == 8)) { set_error(who, "D must be 1,2,3,4 or 8"); return GSPL_ERR_UNSUPPORTED; }
@@ -332,30 +326,27 @@ extern "C" int gspl_composite_fwd(int N, int64_t n_isects, int D, int mode, int 
                                   const int32_t* offsets, const int32_t* flatten_ids,
                                   float* out_colors, float* out_alphas, float* final_Ts, int32_t* last_ids,
                                   uint8_t* hit_flags, void* stream) {
-    return gspl::composite_fwd_impl(N, n_isects, D, mode, layout, means2d, conics, colors, opacities, backgrounds, width, height, tile_size, tile_w, tile_h,
-                                    offsets, flatten_ids, out_colors, out_alphas, final_Ts, last_ids, hit_flags, stream, nullptr);
+    using namespace gspl;
+    return composite_fwd_impl(N, D, mode, layout, CompositeSplats{means2d, conics, colors, opacities, backgrounds}, ImageSize{width, height},
+                              TileGrid{tile_size, tile_w, tile_h}, TileLists{offsets, flatten_ids, n_isects}, out_colors, out_alphas, final_Ts, last_ids,
+                              hit_flags, stream, nullptr);
 }
 
 // (seg: the fused Inria call's checkpoint state for the segmented backward, gspl_composite.h; NULL = off)
-int gspl::composite_fwd_impl(int N, int64_t n_isects, int D, int mode, int layout,
-                                  const float* means2d, const float* conics, const float* colors,
-                                  const float* opacities, const float* backgrounds,
-                                  int width, int height, int tile_size, int tile_w, int tile_h,
-                                  const int32_t* offsets, const int32_t* flatten_ids,
-                                  float* out_colors, float* out_alphas, float* final_Ts, int32_t* last_ids,
-                                  uint8_t* hit_flags, void* stream, const SegState* seg) {
+int gspl::composite_fwd_impl(int N, int D, int mode, int layout, const CompositeSplats& sp, ImageSize image, TileGrid grid, const TileLists& lists,
+                             float* out_colors, float* out_alphas, float* final_Ts, int32_t* last_ids, uint8_t* hit_flags, void* stream,
+                             const SegState* seg) {
     using namespace gspl;
-    int rc = check_composite_args(N, n_isects, D, mode, layout, width, height, tile_size, tile_w, tile_h, "composite_fwd: bad argument");
+    int rc = check_composite_args(N, lists.n_isects, D, mode, layout, image, grid, "composite_fwd: bad argument");
     if (rc != GSPL_OK) return rc;
-    if (!offsets || !out_colors || !out_alphas || !final_Ts || !last_ids) return fail_arg("composite_fwd: NULL required pointer");
-    if (n_isects != 0 && (!means2d || !conics || !colors || !opacities || !flatten_ids)) return fail_arg("composite_fwd: NULL required pointer");
+    if (!lists.offsets || !out_colors || !out_alphas || !final_Ts || !last_ids) return fail_arg("composite_fwd: NULL required pointer");
+    if (lists.n_isects != 0 && (!sp.means2d || !sp.conics || !sp.colors || !sp.opacities || !lists.flatten_ids)) return fail_arg("composite_fwd: NULL required pointer");
     // the kernel walks 8x8 blocks grouped into 16x16 compute tiles; the lists are those of the caller's tile_size (8, 16 or 32)
-    const ListTiles lt = list_tiles(tile_size, tile_w, tile_h);
-    const int ctw = (width + TILE - 1) / TILE, n_tiles = ctw * ((height + TILE - 1) / TILE);
+    const ListTiles lt = list_tiles(grid);
+    const int ctw = (image.width + TILE - 1) / TILE, n_tiles = ctw * ((image.height + TILE - 1) / TILE);
     hipStream_t s = (hipStream_t)stream;
     return dispatch_composite(D, mode, layout, [&](auto d, auto m, auto chw) {
-        return launch_fwd<d(), m(), chw()>(n_tiles, ctw, width, height, n_isects, means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids,
-                                           out_colors, out_alphas, final_Ts, last_ids, hit_flags, s, lt, seg);
+        return launch_fwd<d(), m(), chw()>(n_tiles, ctw, image, sp, lists, out_colors, out_alphas, final_Ts, last_ids, hit_flags, s, lt, seg);
     });
 }
 
@@ -366,7 +357,7 @@ extern "C" int gspl_composite_scores(int N, int64_t n_isects, int mode,
                                      int32_t* count, float* opacity_sum, float* alpha_sum, float* visibility_sum,
                                      float* weighted_sum, float* dist_sum, void* stream) {
     using namespace gspl;
-    int rc = check_composite_args(N, n_isects, 1, mode, GSPL_LAYOUT_HWC, width, height, tile_size, tile_w, tile_h, "composite_scores: bad argument");
+    int rc = check_composite_args(N, n_isects, 1, mode, GSPL_LAYOUT_HWC, ImageSize{width, height}, TileGrid{tile_size, tile_w, tile_h}, "composite_scores: bad argument");
     if (rc != GSPL_OK) return rc;
     if (tile_size != TILE) { set_error("composite_scores", "the statistics pass is built for tile_size 16"); return GSPL_ERR_UNSUPPORTED; }
     if (N == 0 || n_isects == 0) return GSPL_OK;
@@ -374,11 +365,9 @@ extern "C" int gspl_composite_scores(int N, int64_t n_isects, int mode,
     if (weighted_sum && !pixel_weights) return fail_arg("composite_scores: weighted_sum needs pixel_weights");
     const int n_tiles = tile_w * tile_h;
     hipStream_t s = (hipStream_t)stream;
-    if (mode == GSPL_MODE_GSPLAT)
-        hipLaunchKernelGGL(composite_scores_kernel<GSPL_MODE_GSPLAT>, dim3(4 * n_tiles), dim3(64), 0, s, n_tiles, tile_w, width, height, n_isects, means2d, conics,
+    dispatch_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL(composite_scores_kernel<m()>, dim3(4 * n_tiles), dim3(64), 0, s, n_tiles, tile_w, width, height, n_isects, means2d, conics,
                            opacities, offsets, flatten_ids, pixel_weights, count, opacity_sum, alpha_sum, visibility_sum, weighted_sum, dist_sum);
-    else
-        hipLaunchKernelGGL(composite_scores_kernel<GSPL_MODE_INRIA>, dim3(4 * n_tiles), dim3(64), 0, s, n_tiles, tile_w, width, height, n_isects, means2d, conics,
-                           opacities, offsets, flatten_ids, pixel_weights, count, opacity_sum, alpha_sum, visibility_sum, weighted_sum, dist_sum);
+    });
     return check_launch("composite_scores");
 }

@@ -545,15 +545,13 @@ __global__ __launch_bounds__(64) void composite_bwd_block_kernel(
 }
 
 template <int D, int MODE, bool CHW, bool PACKED = false>
-static int launch_bwd(bool absgrad, int n_tiles, int tile_w, int width, int height, int64_t n_isects,
-                      const float* means2d, const float* conics, const float* colors, const float* opacities,
-                      const float* backgrounds, const int32_t* offsets, const int32_t* flatten_ids,
+static int launch_bwd(bool absgrad, int n_tiles, int tile_w, ImageSize image, const CompositeSplats& sp, const TileLists& lists,
                       const float* final_Ts, const int32_t* last_ids,
                       const float* v_out_colors, const float* v_out_alphas,
                       float* v_means2d, float* v_means2d_abs, float* v_conics, float* v_colors, float* v_opacities,
                       hipStream_t s, int packed_stride, uint8_t* hit_flags, ListTiles lt, const SegState* seg_in = nullptr) {
-#define GSPL_BWD_ARGS n_tiles, tile_w, width, height, n_isects, means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids, \
-                      final_Ts, last_ids, v_out_colors, v_out_alphas, v_means2d, v_means2d_abs, v_conics, v_colors, v_opacities,   \
+#define GSPL_BWD_ARGS n_tiles, tile_w, image.width, image.height, lists.n_isects, sp.means2d, sp.conics, sp.colors, sp.opacities, sp.backgrounds, \
+                      lists.offsets, lists.flatten_ids, final_Ts, last_ids, v_out_colors, v_out_alphas, v_means2d, v_means2d_abs, v_conics, v_colors, v_opacities,   \
                       packed_stride, hit_flags
     if (lt.log2 != 4) {       // lists on 8- or 32-pixel tiles: the block-wise compatibility kernel
         if (absgrad) hipLaunchKernelGGL((composite_bwd_block_kernel<D, MODE, CHW, true, PACKED>), dim3(4 * n_tiles), dim3(64), 0, s, GSPL_BWD_ARGS, lt);
@@ -589,19 +587,21 @@ extern "C" int gspl_composite_bwd(int N, int64_t n_isects, int D, int mode, int 
                                   float* v_means2d, float* v_means2d_abs,
                                   float* v_conics, float* v_colors, float* v_opacities, uint8_t* hit_flags, void* stream) {
     using namespace gspl;
-    int rc = check_composite_args(N, n_isects, D, mode, layout, width, height, tile_size, tile_w, tile_h, "composite_bwd: bad argument");
+    const ImageSize image{width, height};
+    const TileGrid grid{tile_size, tile_w, tile_h};
+    int rc = check_composite_args(N, n_isects, D, mode, layout, image, grid, "composite_bwd: bad argument");
     if (rc != GSPL_OK) return rc;
     if (n_isects == 0 || N == 0) return GSPL_OK;
     if (!means2d || !conics || !colors || !opacities || !offsets || !flatten_ids || !final_Ts || !last_ids ||
         !v_out_colors || !v_means2d || !v_conics || !v_colors || !v_opacities)
         return fail_arg("composite_bwd: NULL required pointer");
-    const ListTiles lt = list_tiles(tile_size, tile_w, tile_h);
+    const ListTiles lt = list_tiles(grid);
     const int ctw = (width + TILE - 1) / TILE, n_tiles = ctw * ((height + TILE - 1) / TILE);      // 16x16 compute tiles
     hipStream_t s = (hipStream_t)stream;
     const bool absgrad = v_means2d_abs != nullptr;
     return dispatch_composite(D, mode, layout, [&](auto d, auto m, auto chw) {
-        return launch_bwd<d(), m(), chw()>(absgrad, n_tiles, ctw, width, height, n_isects, means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids,
-                                           final_Ts, last_ids, v_out_colors, v_out_alphas, v_means2d, v_means2d_abs, v_conics, v_colors, v_opacities, s, 0,
+        return launch_bwd<d(), m(), chw()>(absgrad, n_tiles, ctw, image, CompositeSplats{means2d, conics, colors, opacities, backgrounds},
+                                           TileLists{offsets, flatten_ids, n_isects}, final_Ts, last_ids, v_out_colors, v_out_alphas, v_means2d, v_means2d_abs, v_conics, v_colors, v_opacities, s, 0,
                                            hit_flags, lt);
     });
 }
@@ -687,28 +687,25 @@ extern "C" int gspl_composite_bwd_packed(int N, int64_t n_isects, int D, int mod
                                          const float* final_Ts, const int32_t* last_ids,
                                          const float* v_out_colors, const float* v_out_alphas,
                                          float* v_packed, int packed_stride, int absgrad, uint8_t* hit_flags, void* stream) {
-    return gspl::composite_bwd_packed_impl(N, n_isects, D, mode, layout, means2d, conics, colors, opacities, backgrounds, width, height, tile_size, tile_w,
-                                           tile_h, offsets, flatten_ids, final_Ts, last_ids, v_out_colors, v_out_alphas, v_packed, packed_stride, absgrad,
-                                           hit_flags, stream, nullptr);
+    using namespace gspl;
+    return composite_bwd_packed_impl(N, D, mode, layout, CompositeSplats{means2d, conics, colors, opacities, backgrounds}, ImageSize{width, height},
+                                     TileGrid{tile_size, tile_w, tile_h}, TileLists{offsets, flatten_ids, n_isects}, final_Ts, last_ids, v_out_colors,
+                                     v_out_alphas, v_packed, packed_stride, absgrad, hit_flags, stream, nullptr);
 }
 
-int gspl::composite_bwd_packed_impl(int N, int64_t n_isects, int D, int mode, int layout,
-                                         const float* means2d, const float* conics, const float* colors,
-                                         const float* opacities, const float* backgrounds,
-                                         int width, int height, int tile_size, int tile_w, int tile_h,
-                                         const int32_t* offsets, const int32_t* flatten_ids,
-                                         const float* final_Ts, const int32_t* last_ids,
-                                         const float* v_out_colors, const float* v_out_alphas,
-                                         float* v_packed, int packed_stride, int absgrad, uint8_t* hit_flags, void* stream, const SegState* seg) {
+int gspl::composite_bwd_packed_impl(int N, int D, int mode, int layout, const CompositeSplats& sp, ImageSize image, TileGrid grid, const TileLists& lists,
+                                    const float* final_Ts, const int32_t* last_ids, const float* v_out_colors, const float* v_out_alphas,
+                                    float* v_packed, int packed_stride, int absgrad, uint8_t* hit_flags, void* stream, const SegState* seg) {
     using namespace gspl;
-    int rc = check_composite_args(N, n_isects, D, mode, layout, width, height, tile_size, tile_w, tile_h, "composite_bwd_packed: bad argument");
+    const int64_t n_isects = lists.n_isects;
+    int rc = check_composite_args(N, n_isects, D, mode, layout, image, grid, "composite_bwd_packed: bad argument");
     if (rc != GSPL_OK) return rc;
     if (packed_stride < 6 + D + (absgrad ? 2 : 0)) return fail_arg("composite_bwd_packed: packed_stride smaller than the row");
     if (n_isects == 0 || N == 0) return GSPL_OK;
-    if (!means2d || !conics || !colors || !opacities || !offsets || !flatten_ids || !final_Ts || !last_ids || !v_out_colors || !v_packed)
+    if (!sp.means2d || !sp.conics || !sp.colors || !sp.opacities || !lists.offsets || !lists.flatten_ids || !final_Ts || !last_ids || !v_out_colors || !v_packed)
         return fail_arg("composite_bwd_packed: NULL required pointer");
-    const ListTiles lt = list_tiles(tile_size, tile_w, tile_h);
-    const int ctw = (width + TILE - 1) / TILE, n_tiles = ctw * ((height + TILE - 1) / TILE);      // 16x16 compute tiles
+    const ListTiles lt = list_tiles(grid);
+    const int ctw = (image.width + TILE - 1) / TILE, n_tiles = ctw * ((image.height + TILE - 1) / TILE);      // 16x16 compute tiles
     hipStream_t s = (hipStream_t)stream;
     const bool ag = absgrad != 0;
     // deterministic mode (see gspl_set_deterministic below): rows per list entry, then an ordered reduction per splat
@@ -727,12 +724,12 @@ int gspl::composite_bwd_packed_impl(int N, int64_t n_isects, int D, int mode, in
         seg = nullptr;      // (rows per list entry, one writer each: the plain walk)
     }
     rc = dispatch_composite(D, mode, layout, [&](auto d, auto m, auto chw) {
-        return launch_bwd<d(), m(), chw(), true>(ag, n_tiles, ctw, width, height, n_isects, means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids,
+        return launch_bwd<d(), m(), chw(), true>(ag, n_tiles, ctw, image, sp, lists,
                                                  final_Ts, last_ids, v_out_colors, v_out_alphas, v_packed, nullptr, nullptr, nullptr, nullptr, s, packed_stride,
                                                  hit_flags, lt, seg);
     });
     if (ordered) {
-        if (rc == GSPL_OK) rc = ordered_reduce(N, n_isects, nv, flatten_ids, entries, v_packed_out, packed_stride_out, s, "composite_bwd_packed(ordered reduce)");
+        if (rc == GSPL_OK) rc = ordered_reduce(N, n_isects, nv, lists.flatten_ids, entries, v_packed_out, packed_stride_out, s, "composite_bwd_packed(ordered reduce)");
         (void)hipFreeAsync(entries, s);
     }
     return rc;

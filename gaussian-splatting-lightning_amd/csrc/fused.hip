@@ -61,11 +61,30 @@ static bool wait_for_ticket(const int64_t* host, unsigned long long ticket, hipS
         }
     }
 }
+// One lazily initialised T per device, for the process.  with(): f(the current device's T) under the table's lock, after init(T&) has
+// once succeeded on that device; `fallback` for a device outside the table or an initialisation that failed (HIP's error cleared).
+template <class T>
+struct PerDevice {
+    std::mutex mu;
+    T slot[64] = {};
+    bool ready[64] = {};
+    template <class R, class Init, class F>
+    R with(R fallback, Init&& init, F&& f) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return fallback;
+        std::lock_guard<std::mutex> lk(mu);
+        if (!ready[dev]) {
+            if (!init(slot[dev])) { (void)hipGetLastError(); return fallback; }
+            ready[dev] = true;
+        }
+        return f(slot[dev]);
+    }
+};
+
 // Segmented backward, adaptive (gspl_composite.h): one word of pinned host memory per device that the backward kernels raise when a
 // tile's walk is longer than a segment (written from the device, read by the host WITHOUT a synchronisation before a later forward —
 // whenever it lands), and the number of frames the segmented form stays on after the word was last seen raised.  Process-wide:
 // autograd runs the backward on a thread of its own.
-static std::mutex g_seg_mu;
 // Per device: a ring of pinned host words the forward kernels store their verdicts into ((ticket << 1) | tail, about the PREVIOUS frame's
 // backward), the view each slot's verdict is about, the verdicts per view, and the stream-level stickiness for views without one.
 static constexpr unsigned SEG_RING = 16;
@@ -78,65 +97,61 @@ struct SegAdaptive {
     int sticky = 0;
     std::unordered_map<uintptr_t, uint8_t> verdict;      // view -> 1 tail / 0 no tail
 };
-static SegAdaptive g_seg[64];
+static PerDevice<SegAdaptive> g_seg;
 // Called by the forward of a frame that may be segmented: collect the verdicts that have landed, decide for `view`, and hand out the ring
 // slot + ticket this forward's kernel reports under.
 static bool seg_decide(bool force, uintptr_t view, uint32_t** slot_out, uint32_t* ticket_out) {
     *slot_out = nullptr; *ticket_out = 0u;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return force;
-    std::lock_guard<std::mutex> lk(g_seg_mu);
-    SegAdaptive& a = g_seg[dev];
-    if (!a.ring) {
+    auto ring = [](SegAdaptive& a) {
         void* q = nullptr;
-        if (hipHostMalloc(&q, SEG_RING * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return force; }
+        if (hipHostMalloc(&q, SEG_RING * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) return false;
         a.ring = (uint32_t*)q;
         for (unsigned i = 0; i < SEG_RING; ++i) a.ring[i] = 0u;
-    }
-    for (unsigned i = 0; i < SEG_RING; ++i) {
-        if (!a.slot_ticket[i]) continue;
-        const uint32_t v = __atomic_load_n(a.ring + i, __ATOMIC_RELAXED);
-        if ((v >> 1) != (a.slot_ticket[i] & 0x7fffffffu)) continue;      // not landed yet
-        const bool tail = (v & 1u) != 0u;
-        if (a.slot_view[i]) {
-            if (a.verdict.size() > 65536) a.verdict.clear();
-            a.verdict[a.slot_view[i]] = tail ? 1 : 0;
+        return true;
+    };
+    return g_seg.with(force, ring, [&](SegAdaptive& a) {
+        for (unsigned i = 0; i < SEG_RING; ++i) {
+            if (!a.slot_ticket[i]) continue;
+            const uint32_t v = __atomic_load_n(a.ring + i, __ATOMIC_RELAXED);
+            if ((v >> 1) != (a.slot_ticket[i] & 0x7fffffffu)) continue;      // not landed yet
+            const bool tail = (v & 1u) != 0u;
+            if (a.slot_view[i]) {
+                if (a.verdict.size() > 65536) a.verdict.clear();
+                a.verdict[a.slot_view[i]] = tail ? 1 : 0;
+            }
+            if (tail) a.sticky = 64;
+            a.slot_ticket[i] = 0u;
         }
-        if (tail) a.sticky = 64;
-        a.slot_ticket[i] = 0u;
-    }
-    bool on = force;
-    const auto it = view ? a.verdict.find(view) : a.verdict.end();
-    if (it != a.verdict.end()) on = on || it->second != 0;
-    else on = on || a.sticky > 0;
-    if (a.sticky > 0) --a.sticky;
-    // this forward's kernel judges the backward of the previous forward's view
-    const unsigned slot = a.next % SEG_RING;
-    const uint32_t ticket = a.next & 0x7fffffffu;
-    ++a.next; if ((a.next & 0x7fffffffu) == 0u) a.next = 1;
-    a.slot_ticket[slot] = ticket;              // (an older verdict still waited for in this slot is given up: it never landed in 16 frames)
-    a.slot_view[slot] = a.prev_view;
-    a.prev_view = view;
-    *slot_out = a.ring + slot; *ticket_out = ticket;
-    return on;
+        bool on = force;
+        const auto it = view ? a.verdict.find(view) : a.verdict.end();
+        if (it != a.verdict.end()) on = on || it->second != 0;
+        else on = on || a.sticky > 0;
+        if (a.sticky > 0) --a.sticky;
+        // this forward's kernel judges the backward of the previous forward's view
+        const unsigned slot = a.next % SEG_RING;
+        const uint32_t ticket = a.next & 0x7fffffffu;
+        ++a.next; if ((a.next & 0x7fffffffu) == 0u) a.next = 1;
+        a.slot_ticket[slot] = ticket;              // (an older verdict still waited for in this slot is given up: it never landed in 16 frames)
+        a.slot_view[slot] = a.prev_view;
+        a.prev_view = view;
+        *slot_out = a.ring + slot; *ticket_out = ticket;
+        return on;
+    });
 }
 // the table the backward workgroups leave their walk lengths in (SEG_WALK_SLOTS rows of four words), one per device, zero at first
-static uint32_t* g_seg_walk[64] = {};
+static PerDevice<uint32_t*> g_seg_walk;
 static uint32_t* seg_walk_words() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    std::lock_guard<std::mutex> lk(g_seg_mu);
-    if (!g_seg_walk[dev]) {
+    auto zeroed = [](uint32_t*& words) {
         void* q = nullptr;
         const size_t bytes = (size_t)SEG_WALK_SLOTS * 4 * sizeof(uint32_t);
         if (hipMalloc(&q, bytes) != hipSuccess || hipMemset(q, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-            (void)hipGetLastError();
             if (q) (void)hipFree(q);
-            return nullptr;
+            return false;
         }
-        g_seg_walk[dev] = (uint32_t*)q;
-    }
-    return g_seg_walk[dev];
+        words = (uint32_t*)q;
+        return true;
+    };
+    return g_seg_walk.with((uint32_t*)nullptr, zeroed, [](uint32_t* words) { return words; });
 }
 
 static unsigned long long next_ticket() {
@@ -162,18 +177,16 @@ static FrameEvents& frame_events() {
 // A LOW-priority stream per device for the colour kernel (created once, never destroyed).  The colour kernel is a 70-90 us
 // bandwidth stream that runs next to the latency-bound key pass and depth sort; at equal priority it takes half the machine
 // from kernels that are on the critical path.  (torch.cuda.Stream cannot ask for a priority below the default.)
+static PerDevice<hipStream_t> g_low_priority_streams;
 extern "C" void* gspl_low_priority_stream(void) {
-    static std::mutex mu;
-    static hipStream_t streams[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!streams[dev]) {
+    auto create = [](hipStream_t& st) {
         int least = 0, greatest = 0;
         (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        if (hipStreamCreateWithPriority(&streams[dev], hipStreamNonBlocking, least) != hipSuccess) { (void)hipGetLastError(); streams[dev] = nullptr; }
-    }
-    return streams[dev];
+        if (hipStreamCreateWithPriority(&st, hipStreamNonBlocking, least) == hipSuccess) return true;
+        st = nullptr;
+        return false;
+    };
+    return g_low_priority_streams.with((void*)nullptr, create, [](hipStream_t st) { return (void*)st; });
 }
 
 // Optional timing of the two compositing launches INSIDE the fused calls (bench.py's roofline: the launches cannot be bracketed
@@ -237,6 +250,106 @@ extern "C" size_t gspl_rasterize_inria_image_bytes(int width, int height) {
     return gspl::image_layout((size_t)width * height, (size_t)((width + 15) / 16) * ((height + 15) / 16)).total;
 }
 
+namespace gspl {
+
+static void carve_inria_state(gspl_inria_state* st, char* geom, const GeomLayout& g, char* img, const ImageLayout& im) {
+    st->means2d = (float*)(geom + g.means2d); st->depths = (float*)(geom + g.depths); st->conics = (float*)(geom + g.conics);
+    st->colors = (float*)(geom + g.colors); st->clamped = (uint8_t*)(geom + g.clamped); st->cov3d = (float*)(geom + g.cov3d);
+    st->sh_jac = (float*)(geom + g.sh_jac);
+    st->alphas = (float*)(img + im.alphas); st->final_Ts = (float*)(img + im.final_Ts); st->last_ids = (int32_t*)(img + im.last_ids);
+    st->offsets = (int32_t*)(img + im.offsets);
+}
+
+// The wait for the scan's ticket as a scope, opened where the scan is enqueued: every way out of the scope has waited for the scan,
+// because `host` is the thread's one block (pinned_words), free again after the call.
+struct TicketWait {
+    const int64_t* host; hipStream_t s;
+    const unsigned long long ticket = next_ticket();
+    bool waited = false, arrived = false;
+    TicketWait(const int64_t* h, hipStream_t st) : host(h), s(st) {}
+    TicketWait(const TicketWait&) = delete;
+    bool wait() {      // whether the ticket arrived
+        if (!waited) { arrived = wait_for_ticket(host, ticket, s); waited = true; }
+        return arrived;
+    }
+    ~TicketWait() { (void)wait(); }
+};
+static int list_length_never_arrived(hipStream_t s) {
+    const char* what = "rasterize_inria_fwd: the list length never arrived";
+    return check_hip(hipStreamSynchronize(s), what) ? GSPL_ERR_LAUNCH : fail_arg(what);
+}
+
+// Segmented backward (gspl_composite.h): checkpoints + the frame's counters, sized by the list CAPACITY (known before the lists
+// are: the guess, or the real length), from one allocation kept until the backward.  Off with GSPL_INRIA_NO_SEGMENTS, in the
+// deterministic mode (its backward writes one row per list entry) and when the caller's allocator says no.
+// (with or without checkpoints the forward kernel reduces the walk table the last backward left and reports its verdict)
+struct SegPlan {
+    bool adaptive = false, want = false;      // what seg_decide returned, with the ring slot + ticket this forward reports under
+    uint32_t* verdict_slot = nullptr;
+    uint32_t verdict_ticket = 0u;
+    uint4* packed_zero = nullptr;             // the backward's packed rows, cleared by the forward's compositing kernel (GSPL_INRIA_WILL_BACKWARD, ABI 35)
+    uint32_t packed_n16 = 0u;
+    SegState seg = {};
+    void ask_packed_rows(size_t row_bytes, gspl_alloc_fn alloc, void* alloc_ctx, gspl_inria_state* st) {
+        const size_t bytes = (row_bytes + 15) & ~(size_t)15;
+        packed_zero = (uint4*)alloc(alloc_ctx, GSPL_BUF_PACKED, bytes);
+        if (packed_zero && bytes / 16 <= 0xffffffffull) { packed_n16 = (uint32_t)(bytes / 16); st->flags |= GSPL_INRIA_PACKED_READY; }
+        else packed_zero = nullptr;
+    }
+    // what the compositing launch of lists with room for `cap` entries takes (NULL: nothing to do); asks for the checkpoint block
+    const SegState* for_capacity(int64_t cap, bool invd, gspl_alloc_fn alloc, void* alloc_ctx, gspl_inria_state* st) {
+        seg = SegState{};
+        seg.zero_p = packed_zero; seg.zero_n16 = packed_n16;
+        if (adaptive) { seg.walk = seg_walk_words(); seg.host_flag = verdict_slot; seg.ticket = verdict_ticket; }
+        st->seg_ckpt = nullptr; st->seg_words = nullptr; st->seg_slots = 0u;
+        if (!want || cap <= SEG) return (adaptive || packed_zero) ? &seg : nullptr;
+        const uint32_t slots = (uint32_t)(cap >> SEG_LOG2) + 2u;
+        const size_t words = 2 + (size_t)slots;
+        const size_t head = up256(words * sizeof(uint32_t));
+        // (with invd: one more float per checkpoint, the inverse-depth channel, after the float4s)
+        char* blk = (char*)alloc(alloc_ctx, GSPL_BUF_CHECKPOINTS, head + (size_t)slots * 256 * (sizeof(float4) + (invd ? sizeof(float) : 0)));
+        if (!blk) return (adaptive || packed_zero) ? &seg : nullptr;
+        uint32_t* wds = (uint32_t*)blk;
+        seg.words = wds; seg.slots = slots;      // (the item counter is cleared by the forward kernel itself)
+        seg.ckpt = (float4*)(blk + head);
+        seg.ckpt_x = invd ? (float*)(seg.ckpt + (size_t)slots * 256) : nullptr;
+        st->seg_ckpt = seg.ckpt; st->seg_words = wds; st->seg_slots = slots;
+        return &seg;
+    }
+};
+
+// The colour chain of a frame, behind its geometry kernel: the SH kernel (and, with GSPL_INRIA_INVDEPTH, the [N,4] rows compositing reads),
+// on the side stream when there is one.  *ev_col: what the caller's stream then waits for before compositing (NULL: same stream).
+static int inria_colours_launch(int N, const InriaParams& p, const InriaCamera& cam, const float* colors_precomp, int32_t* radii, gspl_inria_state* st,
+                                float* colors3, hipStream_t s, hipStream_t ss, hipEvent_t* ev_col) {
+    FrameEvents& fe = frame_events();
+    if (!fe.ok) return check_hip(hipGetLastError(), "rasterize_inria_fwd: event");
+    const bool side = ss && ss != s;
+    if (side) {
+        (void)hipEventRecord(fe.geo, s);
+        (void)hipStreamWaitEvent(ss, fe.geo, 0);
+    }
+    hipStream_t cs = side ? ss : s;
+    int rc = gspl_inria_preprocess_fwd(N, p.degree, p.n_coeffs, p.means, p.scales, p.quats, p.cov3d, p.shs, p.shs_rest, colors_precomp, cam.viewmatrix,
+                                       cam.projmatrix, cam.campos, cam.width, cam.height, 16, cam.tanfovx, cam.tanfovy, cam.scale_modifier, radii, st->means2d,
+                                       st->depths, st->conics, colors3, st->clamped, st->cov3d, st->sh_jac, GSPL_INRIA_COLOURS, cs);
+    if (rc == GSPL_OK && (st->flags & GSPL_INRIA_INVDEPTH)) rc = inria_invdepth_rows_launch(N, radii, colors3, st->depths, st->colors, cs);
+    if (rc == GSPL_OK && side) { (void)hipEventRecord(fe.col, cs); *ev_col = fe.col; }
+    return rc;
+}
+
+// the frame's compositing launch (n_isects < 0: the list length is on the device); colours are ready before compositing reads them
+static int inria_composite_launch(int N, int D, const gspl_inria_state* st, const float* bg, int64_t n_isects, float* out_color,
+                                  hipEvent_t ev_col, hipStream_t s, const SegState* sg) {
+    if (ev_col) (void)hipStreamWaitEvent(s, ev_col, 0);
+    ProfScope prof(0, s);
+    return composite_fwd_impl(N, D, GSPL_MODE_INRIA, GSPL_LAYOUT_CHW, CompositeSplats{st->means2d, st->conics, st->colors, st->opacities, bg},
+                              ImageSize{st->width, st->height}, tile_grid16(st->width, st->height), TileLists{st->offsets, st->flatten_ids, n_isects},
+                              out_color, st->alphas, st->final_Ts, st->last_ids, nullptr, s, sg);
+}
+
+}  // namespace gspl
+
 extern "C" int gspl_rasterize_inria_fwd(
     int N, int degree, int n_coeffs,
     const float* means3D, const float* scales, const float* rotations, const float* cov3D_precomp,
@@ -246,9 +359,10 @@ extern "C" int gspl_rasterize_inria_fwd(
     gspl_alloc_fn alloc, void* alloc_ctx, int64_t capacity_hint,
     float* out_color, int32_t* radii, gspl_inria_state* st, void* stream, void* side_stream) {
     using namespace gspl;
+    const char* no_block = "rasterize_inria_fwd: allocation call-back returned NULL";
     if (N < 0 || width <= 0 || height <= 0 || !alloc || !st || !out_color) return fail_arg("rasterize_inria_fwd: bad argument");
     if (N > 0 && (!means3D || !opacities || !radii || !viewmatrix || !projmatrix || !campos)) return fail_arg("rasterize_inria_fwd: NULL required pointer");
-    const int tile = 16, tile_w = (width + 15) / 16, tile_h = (height + 15) / 16, n_tiles = tile_w * tile_h;
+    const TileGrid grid = tile_grid16(width, height);
     hipStream_t s = (hipStream_t)stream, ss = (hipStream_t)side_stream;
     const int flags = st->flags;
     if (flags & ~(GSPL_INRIA_RAW_PARAMS | GSPL_INRIA_NO_SEGMENTS | GSPL_INRIA_FORCE_SEGMENTS | GSPL_INRIA_WILL_BACKWARD | GSPL_INRIA_ANTIALIAS |
@@ -263,226 +377,100 @@ extern "C" int gspl_rasterize_inria_fwd(
     st->N = N; st->width = width; st->height = height;
     const size_t n = (size_t)(N > 0 ? N : 1);
     const GeomLayout g = geom_layout(n, invd);
-    const ImageLayout im = image_layout((size_t)width * height, (size_t)n_tiles);
+    const ImageLayout im = image_layout((size_t)width * height, (size_t)grid.n());
     char* geom = (char*)alloc(alloc_ctx, GSPL_BUF_GEOMETRY, g.total);
     char* img = (char*)alloc(alloc_ctx, GSPL_BUF_IMAGE, im.total);
-    if (!geom || !img) return fail_arg("rasterize_inria_fwd: allocation call-back returned NULL");
-    st->means2d = (float*)(geom + g.means2d); st->depths = (float*)(geom + g.depths); st->conics = (float*)(geom + g.conics);
-    st->colors = (float*)(geom + g.colors); st->clamped = (uint8_t*)(geom + g.clamped); st->cov3d = (float*)(geom + g.cov3d);
-    st->sh_jac = (float*)(geom + g.sh_jac);
+    if (!geom || !img) return fail_arg(no_block);
+    carve_inria_state(st, geom, g, img, im);
     float* colors3 = st->colors;                  // where the colour kernel writes; with invd compositing reads the [N,4] rows
     if (invd) st->colors = (float*)(geom + g.colors4);
     const float* raw_opacities = (raw || aa) ? opacities : nullptr;      // (with aa: the caller's opacities, raw or activated)
     if (raw || aa) opacities = (float*)(geom + g.opac);          // from here on: what binning and compositing read
     st->opacities = const_cast<float*>(opacities);
-    st->alphas = (float*)(img + im.alphas); st->final_Ts = (float*)(img + im.final_Ts); st->last_ids = (int32_t*)(img + im.last_ids);
-    st->offsets = (int32_t*)(img + im.offsets);
-    // Segmented backward (gspl_composite.h): checkpoints + the frame's counters, sized by the list CAPACITY (known before the lists
-    // are: the guess, or the real length), from one allocation kept until the backward.  Off with GSPL_INRIA_NO_SEGMENTS, in the
-    // deterministic mode (its backward writes one row per list entry) and when the caller's allocator says no.
-    SegState seg = {};
-    const bool adaptive = !(flags & GSPL_INRIA_NO_SEGMENTS) && gspl_get_deterministic() == 0;
-    uint32_t* verdict_slot = nullptr;
-    uint32_t verdict_ticket = 0u;
-    const bool want_seg = adaptive && seg_decide((flags & GSPL_INRIA_FORCE_SEGMENTS) != 0, (uintptr_t)viewmatrix, &verdict_slot, &verdict_ticket);
-    // (with or without checkpoints the forward kernel reduces the walk table the last backward left and reports its verdict)
-    // the backward's packed rows, cleared by the forward's compositing kernel (GSPL_INRIA_WILL_BACKWARD, ABI 35)
-    uint4* packed_zero = nullptr;
-    uint32_t packed_n16 = 0u;
-    if ((flags & GSPL_INRIA_WILL_BACKWARD) && N > 0) {
-        const size_t bytes = ((size_t)N * prow * sizeof(float) + 15) & ~(size_t)15;
-        packed_zero = (uint4*)alloc(alloc_ctx, GSPL_BUF_PACKED, bytes);
-        if (packed_zero && bytes / 16 <= 0xffffffffull) { packed_n16 = (uint32_t)(bytes / 16); st->flags |= GSPL_INRIA_PACKED_READY; }
-        else packed_zero = nullptr;
+    SegPlan plan;
+    plan.adaptive = !(flags & GSPL_INRIA_NO_SEGMENTS) && gspl_get_deterministic() == 0;
+    plan.want = plan.adaptive && seg_decide((flags & GSPL_INRIA_FORCE_SEGMENTS) != 0, (uintptr_t)viewmatrix, &plan.verdict_slot, &plan.verdict_ticket);
+    if ((flags & GSPL_INRIA_WILL_BACKWARD) && N > 0) plan.ask_packed_rows((size_t)N * prow * sizeof(float), alloc, alloc_ctx, st);
+    const BinSplats bins{N, GSPL_MODE_INRIA, st->means2d, radii, st->depths, st->conics, opacities};
+    const BinOrder ord{(int32_t*)(geom + g.order), (int64_t*)(geom + g.cum), (int32_t*)(geom + g.big_list), geom + g.spans};
+    if (N == 0) {
+        const int rc = bin_lists_known(BinSplats{0, GSPL_MODE_INRIA}, BinOrder{}, grid, 0, alloc, alloc_ctx, &st->flatten_ids, st->offsets, s, "rasterize_inria_fwd");
+        return rc != GSPL_OK ? rc : inria_composite_launch(N, D, st, bg, 0, out_color, nullptr, s, nullptr);
     }
-    auto make_seg = [&](int64_t cap) -> const SegState* {
-        seg = SegState{};
-        seg.zero_p = packed_zero; seg.zero_n16 = packed_n16;
-        if (adaptive) { seg.walk = seg_walk_words(); seg.host_flag = verdict_slot; seg.ticket = verdict_ticket; }
-        st->seg_ckpt = nullptr; st->seg_words = nullptr; st->seg_slots = 0u;
-        if (!want_seg || cap <= SEG) return (adaptive || packed_zero) ? &seg : nullptr;
-        const uint32_t slots = (uint32_t)(cap >> SEG_LOG2) + 2u;
-        const size_t words = 2 + (size_t)slots;
-        const size_t head = up256(words * sizeof(uint32_t));
-        // (with invd: one more float per checkpoint, the inverse-depth channel, after the float4s)
-        char* blk = (char*)alloc(alloc_ctx, GSPL_BUF_CHECKPOINTS, head + (size_t)slots * 256 * (sizeof(float4) + (invd ? sizeof(float) : 0)));
-        if (!blk) return (adaptive || packed_zero) ? &seg : nullptr;
-        uint32_t* wds = (uint32_t*)blk;
-        seg.words = wds; seg.slots = slots;      // (the item counter is cleared by the forward kernel itself)
-        seg.ckpt = (float4*)(blk + head);
-        seg.ckpt_x = invd ? (float*)(seg.ckpt + (size_t)slots * 256) : nullptr;
-        st->seg_ckpt = seg.ckpt; st->seg_words = wds; st->seg_slots = slots;
-        return &seg;
-    };
-    int32_t* order = (int32_t*)(geom + g.order);
-    int64_t* cum = (int64_t*)(geom + g.cum);
-    int32_t* big_list = (int32_t*)(geom + g.big_list);
-    void* spans = geom + g.spans;
-    int rc = GSPL_OK;
+    // every block whose size is known up front is asked for BEFORE the first launch: an allocation call-back costs the host
+    // 5-10 us (it runs the caller's allocator), and between two launches that is a 6 us bubble on the device
+    const size_t ws1_bytes = gspl_bin_workspace_bytes(N, 0);
+    char* ws1 = (char*)alloc(alloc_ctx, GSPL_BUF_BINNING, ws1_bytes);
+    if (!ws1) return fail_arg(no_block);
+    const int64_t capacity = capacity_hint > 0 ? capacity_hint : 0;
+    const size_t ws2_bytes = capacity ? gspl_bin_workspace_bytes(N, capacity) : 0;
+    char* ws2 = capacity ? (char*)alloc(alloc_ctx, GSPL_BUF_LISTS_WORK, ws2_bytes) : nullptr;
+    if (capacity && !ws2) return fail_arg(no_block);
+    int64_t* host = pinned_words();
+    if (!host) return fail_arg("rasterize_inria_fwd: no pinned host word");
+    // geometry; then two independent chains: the colour (SH) kernel on the side stream, the count / depth-sort half of the
+    // binning on the caller's stream; the host meanwhile waits for the one number that sizes the tile sort
+    if (!viewmatrix || !projmatrix) return fail_arg("rasterize_inria_fwd: NULL required pointer");
+    if (!cov3D_precomp && (!scales || !rotations)) return fail_arg("rasterize_inria_fwd: need scales+rotations or cov3D_precomp");
+    // the geometry kernel clears the depth sort's tables, the scan kernel the tile sort's (when its workspace exists by then):
+    // two launches fewer in front of the kernels that fill those tables
+    ZeroJob zero_depth, zero_tile;
+    int rc = bin_depth_header(N, grid.n(), ws1, zero_depth);
+    if (rc == GSPL_OK && ws2) rc = bin_tile_header(N, capacity, grid.n(), ws2, zero_tile);
+    if (rc != GSPL_OK) return rc;
+    const InriaParams params{means3D, scales, rotations, cov3D_precomp, shs, shs_rest, degree, n_coeffs};
+    const InriaCamera cam{viewmatrix, projmatrix, campos, width, height, tanfovx, tanfovy, scale_modifier};
+    rc = inria_geometry_launch(N, params, cam, grid.size, radii, st->means2d, st->depths, st->conics, st->cov3d, raw_opacities, st->opacities, s, zero_depth,
+                               flags & (GSPL_INRIA_RAW_PARAMS | GSPL_INRIA_ANTIALIAS));
+    if (rc != GSPL_OK) return rc;
+    hipEvent_t ev_col = nullptr;
+    rc = inria_colours_launch(N, params, cam, colors_precomp, radii, st, colors3, s, ss, &ev_col);
+    if (rc != GSPL_OK) return rc;
+    TicketWait scan(host, s);      // the scan kernel stores the two numbers, then the ticket, into `host`
+    rc = bin_count_ticket(bins, grid, ord, host, ws1, ws1_bytes, s, scan.ticket, true, zero_tile);
+    if (rc != GSPL_OK) return rc;
     int64_t n_isects = 0;
-    if (N > 0) {
-        // every block whose size is known up front is asked for BEFORE the first launch: an allocation call-back costs the host
-        // 5-10 us (it runs the caller's allocator), and between two launches that is a 6 us bubble on the device
-        const size_t ws1_bytes = gspl_bin_workspace_bytes(N, 0);
-        char* ws1 = (char*)alloc(alloc_ctx, GSPL_BUF_BINNING, ws1_bytes);
-        if (!ws1) return fail_arg("rasterize_inria_fwd: allocation call-back returned NULL");
-        int64_t capacity = 0;
-        char* ws2 = nullptr;
-        size_t ws2_bytes = 0;
-        if (capacity_hint > 0) {
-            capacity = capacity_hint;
-            ws2_bytes = gspl_bin_workspace_bytes(N, capacity);
-            ws2 = (char*)alloc(alloc_ctx, GSPL_BUF_LISTS_WORK, ws2_bytes);
-            if (!ws2) return fail_arg("rasterize_inria_fwd: allocation call-back returned NULL");
-        }
-        int64_t* host = pinned_words();
-        if (!host) return fail_arg("rasterize_inria_fwd: no pinned host word");
-        // geometry; then two independent chains: the colour (SH) kernel on the side stream, the count / depth-sort half of the
-        // binning on the caller's stream; the host meanwhile waits for the one number that sizes the tile sort
-        if (!viewmatrix || !projmatrix) return fail_arg("rasterize_inria_fwd: NULL required pointer");
-        if (!cov3D_precomp && (!scales || !rotations)) return fail_arg("rasterize_inria_fwd: need scales+rotations or cov3D_precomp");
-        // the geometry kernel clears the depth sort's tables, the scan kernel the tile sort's (when its workspace exists by then):
-        // two launches fewer in front of the kernels that fill those tables
-        ZeroJob zero_depth, zero_tile;
-        rc = bin_depth_header(N, tile_w * tile_h, ws1, zero_depth);
-        if (rc == GSPL_OK && ws2) rc = bin_tile_header(N, capacity, tile_w * tile_h, ws2, zero_tile);
+    if (ws2) {
+        // Speculative emission with the caller's guess of the list length.  The host does not wait for the real one: the sort reads it
+        // on the device (the grid is sized by `capacity`), the compositing kernel finds the end of the last list in offsets[n_tiles].
+        // The number is looked at AFTER everything is enqueued — by then the scan has long finished — and only a guess that turns out
+        // too low costs a second round.
+        rc = bin_emit_impl(bins, ord, grid, capacity, ws2, ws2_bytes, s, true);
         if (rc != GSPL_OK) return rc;
-        rc = inria_geometry_launch(N, means3D, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, width, height, tile, tanfovx, tanfovy, scale_modifier,
-                                   radii, st->means2d, st->depths, st->conics, st->cov3d, raw_opacities, st->opacities, s, zero_depth,
-                                   flags & (GSPL_INRIA_RAW_PARAMS | GSPL_INRIA_ANTIALIAS));
+        st->flatten_ids = (int32_t*)alloc(alloc_ctx, GSPL_BUF_LISTS, 4 * (size_t)capacity);
+        if (!st->flatten_ids) return fail_arg(no_block);
+        const SegState* sg = plan.for_capacity(capacity, invd, alloc, alloc_ctx, st);
+        rc = gspl_bin_sort_device_count(N, grid.w, grid.h, ord.cum + (N - 1), capacity, st->flatten_ids, st->offsets, ws2, ws2_bytes, s);
         if (rc != GSPL_OK) return rc;
-        FrameEvents& fe = frame_events();
-        if (!fe.ok) return check_hip(hipGetLastError(), "rasterize_inria_fwd: event");
-        hipEvent_t ev_geo = nullptr, ev_col = nullptr;
-        if (ss && ss != s) {
-            ev_geo = fe.geo; ev_col = fe.col;
-            (void)hipEventRecord(ev_geo, s);
-            (void)hipStreamWaitEvent(ss, ev_geo, 0);
-        }
-        hipStream_t cs = (ss && ss != s) ? ss : s;
-        rc = gspl_inria_preprocess_fwd(N, degree, n_coeffs, means3D, scales, rotations, cov3D_precomp, shs, shs_rest, colors_precomp, viewmatrix, projmatrix,
-                                       campos, width, height, tile, tanfovx, tanfovy, scale_modifier, radii, st->means2d, st->depths, st->conics,
-                                       colors3, st->clamped, st->cov3d, st->sh_jac, GSPL_INRIA_COLOURS, cs);
-        if (rc == GSPL_OK && invd) rc = inria_invdepth_rows_launch(N, radii, colors3, st->depths, st->colors, cs);      // (on the colour stream)
-        if (rc == GSPL_OK && ev_col) (void)hipEventRecord(ev_col, cs);
+        rc = inria_composite_launch(N, D, st, bg, -1, out_color, ev_col, s, sg);
+        const bool arrived = scan.wait();
+        n_isects = host[0];
         if (rc != GSPL_OK) return rc;
-        {
-            const unsigned long long ticket = next_ticket();
-            rc = bin_count_ticket(N, GSPL_MODE_INRIA, st->means2d, radii, st->depths, st->conics, opacities, tile, tile_w, tile_h, order, cum, big_list,
-                                  spans, host, ws1, ws1_bytes, s, ticket, true, zero_tile);      // the scan kernel stores the two numbers, then the ticket, into `host`
-            // every return from here on has waited for the scan: `host` is the thread's one block (pinned_words), free again after the call
-            auto wait_count = [&]() -> bool { return wait_for_ticket(host, ticket, s); };
-            if (rc != GSPL_OK) { (void)wait_count(); return rc; }
-            // speculative emission with the caller's guess of the list length, while the host waits for the real one
-            if (ws2) {
-                rc = bin_emit_impl(N, GSPL_MODE_INRIA, st->means2d, radii, st->conics, opacities, order, cum, big_list, spans, tile, tile_w, tile_h,
-                                   capacity, ws2, ws2_bytes, s, true);
-                if (rc != GSPL_OK) { (void)wait_count(); return rc; }
-            }
-            if (ws2) {
-                // The host does not wait for the list length: the sort reads it on the device (the grid is sized by `capacity`), the
-                // compositing kernel finds the end of the last list in offsets[n_tiles].  The number is looked at AFTER everything is
-                // enqueued — by then the scan has long finished — and only a guess that turns out too low costs a second round.
-                st->flatten_ids = (int32_t*)alloc(alloc_ctx, GSPL_BUF_LISTS, 4 * (size_t)capacity);
-                if (!st->flatten_ids) { (void)wait_count(); return fail_arg("rasterize_inria_fwd: allocation call-back returned NULL"); }
-                const SegState* sg = make_seg(capacity);
-                rc = gspl_bin_sort_device_count(N, tile_w, tile_h, cum + (N - 1), capacity, st->flatten_ids, st->offsets, ws2, ws2_bytes, s);
-                if (rc != GSPL_OK) { (void)wait_count(); return rc; }
-                if (ev_col) (void)hipStreamWaitEvent(s, ev_col, 0);      // colours are ready before compositing reads them
-                {
-                    ProfScope prof(0, s);
-                    rc = composite_fwd_impl(N, -1, D, GSPL_MODE_INRIA, GSPL_LAYOUT_CHW, st->means2d, st->conics, st->colors, opacities, bg, width, height,
-                                            tile, tile_w, tile_h, st->offsets, st->flatten_ids, out_color, st->alphas, st->final_Ts, st->last_ids, nullptr, s, sg);
-                }
-                const bool arrived = wait_count();
-                n_isects = host[0];
-                if (rc != GSPL_OK) return rc;
-                if (!arrived) return check_hip(hipStreamSynchronize(s), "rasterize_inria_fwd: the list length never arrived") ? GSPL_ERR_LAUNCH : fail_arg("rasterize_inria_fwd: the list length never arrived");
-                if (n_isects <= capacity) { st->n_isects = n_isects; return GSPL_OK; }
-                // too low a guess: the frame's lists are redone below with the real length
-            } else {
-                if (!wait_count()) return check_hip(hipStreamSynchronize(s), "rasterize_inria_fwd: the list length never arrived") ? GSPL_ERR_LAUNCH : fail_arg("rasterize_inria_fwd: the list length never arrived");
-                n_isects = host[0];
-            }
-            rc = bin_lists_known(N, GSPL_MODE_INRIA, st->means2d, radii, st->conics, opacities, order, cum, big_list, spans, tile, tile_w, tile_h, n_isects,
-                                 alloc, alloc_ctx, &st->flatten_ids, st->offsets, s, "rasterize_inria_fwd");
-            if (rc != GSPL_OK) return rc;
-            (void)make_seg(n_isects);      // (the checkpoint block: only the compositing launch needs it)
-        }
-        if (ev_col) (void)hipStreamWaitEvent(s, ev_col, 0);      // colours are ready before compositing reads them
+        if (!arrived) return list_length_never_arrived(s);
+        if (n_isects <= capacity) { st->n_isects = n_isects; return GSPL_OK; }
+        // too low a guess: the frame's lists are redone below with the real length
     } else {
-        rc = bin_lists_known(0, GSPL_MODE_INRIA, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, tile, tile_w, tile_h, 0,
-                             alloc, alloc_ctx, &st->flatten_ids, st->offsets, s, "rasterize_inria_fwd");
-        if (rc != GSPL_OK) return rc;
+        if (!scan.wait()) return list_length_never_arrived(s);
+        n_isects = host[0];
     }
+    rc = bin_lists_known(bins, ord, grid, n_isects, alloc, alloc_ctx, &st->flatten_ids, st->offsets, s, "rasterize_inria_fwd");
+    if (rc != GSPL_OK) return rc;
     st->n_isects = n_isects;
-    ProfScope prof(0, s);
-    return composite_fwd_impl(N, n_isects, D, GSPL_MODE_INRIA, GSPL_LAYOUT_CHW, st->means2d, st->conics, st->colors, opacities, bg, width, height, tile,
-                              tile_w, tile_h, st->offsets, st->flatten_ids, out_color, st->alphas, st->final_Ts, st->last_ids, nullptr, s,
-                              (seg.ckpt || seg.walk || seg.zero_p) ? &seg : nullptr);
+    return inria_composite_launch(N, D, st, bg, n_isects, out_color, ev_col, s, plan.for_capacity(n_isects, invd, alloc, alloc_ctx, st));
 }
 
 namespace gspl {
-static int rasterize_inria_bwd_impl(
-    int degree, int n_coeffs,
-    const float* means3D, const float* scales, const float* rotations, const float* shs, const float* shs_rest, const float* opacities,
-    const float* viewmatrix, const float* projmatrix, const float* campos, const float* bg,
-    float tanfovx, float tanfovy, float scale_modifier,
-    const int32_t* radii, const gspl_inria_state* st, const float* v_out_color,
-    float* packed, uint8_t* hit_flags,
-    float* v_means3D, float* v_means2D_ndc, float* v_shs, float* v_shs_rest, float* v_colors_precomp, float* v_opacities,
-    float* v_scales, float* v_rotations, float* v_cov3D, void* stream, const gspl_bwd_adam_plan* plan);
-}
-
-extern "C" int gspl_rasterize_inria_bwd(
-    int degree, int n_coeffs,
-    const float* means3D, const float* scales, const float* rotations, const float* shs, const float* shs_rest, const float* opacities,
-    const float* viewmatrix, const float* projmatrix, const float* campos, const float* bg,
-    float tanfovx, float tanfovy, float scale_modifier,
-    const int32_t* radii, const gspl_inria_state* st, const float* v_out_color,
-    float* packed, uint8_t* hit_flags,
-    float* v_means3D, float* v_means2D_ndc, float* v_shs, float* v_shs_rest, float* v_colors_precomp, float* v_opacities,
-    float* v_scales, float* v_rotations, float* v_cov3D, void* stream) {
-    return gspl::rasterize_inria_bwd_impl(degree, n_coeffs, means3D, scales, rotations, shs, shs_rest, opacities, viewmatrix, projmatrix, campos, bg,
-                                          tanfovx, tanfovy, scale_modifier, radii, st, v_out_color, packed, hit_flags, v_means3D, v_means2D_ndc, v_shs,
-                                          v_shs_rest, v_colors_precomp, v_opacities, v_scales, v_rotations, v_cov3D, stream, nullptr);
-}
-
-// The same backward with the optimizer INSIDE it (VERDICT r4 #2): the per-Gaussian kernels at the end of the backward (SH backward,
-// preprocess backward) apply the Adam update to the parameter rows they have just produced the gradient of, instead of writing
-// 236 B of gradient per Gaussian for a separate optimizer launch to read back.  The parameters are updated IN PLACE; only the
-// screen-space gradient (what the density controller reads, vanilla_density_controller.py:101-123) is written.
-extern "C" int gspl_rasterize_inria_bwd_adam(
-    int degree, int n_coeffs,
-    float* means3D, float* scales, float* rotations, float* shs, float* shs_rest, float* opacities,
-    const float* viewmatrix, const float* projmatrix, const float* campos, const float* bg,
-    float tanfovx, float tanfovy, float scale_modifier,
-    const int32_t* radii, const gspl_inria_state* st, const float* v_out_color,
-    float* packed, uint8_t* hit_flags, float* scratch_means, float* v_means2D_ndc, const gspl_bwd_adam_plan* plan, void* stream) {
-    if (!plan) return gspl::fail_arg("rasterize_inria_bwd_adam: NULL plan");
-    if (!scales || !rotations || !shs || !opacities) return gspl::fail_arg("rasterize_inria_bwd_adam: needs scales, rotations, SH coefficients and opacities");
-    if (st && (st->flags & (GSPL_INRIA_ANTIALIAS | GSPL_INRIA_INVDEPTH)))
-        return gspl::fail_arg("rasterize_inria_bwd_adam: a frame rendered with GSPL_INRIA_ANTIALIAS or GSPL_INRIA_INVDEPTH takes gspl_rasterize_inria_bwd and a separate optimizer");
-    return gspl::rasterize_inria_bwd_impl(degree, n_coeffs, means3D, scales, rotations, shs, shs_rest, opacities, viewmatrix, projmatrix, campos, bg,
-                                          tanfovx, tanfovy, scale_modifier, radii, st, v_out_color, packed, hit_flags, scratch_means, v_means2D_ndc, shs,
-                                          shs_rest, nullptr, opacities, scales, rotations, nullptr, stream, plan);
-}
-
-static int gspl::rasterize_inria_bwd_impl(
-    int degree, int n_coeffs,
-    const float* means3D, const float* scales, const float* rotations, const float* shs, const float* shs_rest, const float* opacities,
-    const float* viewmatrix, const float* projmatrix, const float* campos, const float* bg,
-    float tanfovx, float tanfovy, float scale_modifier,
-    const int32_t* radii, const gspl_inria_state* st, const float* v_out_color,
-    float* packed /* [N, 9] scratch ([N, 10] with GSPL_INRIA_INVDEPTH) */, uint8_t* hit_flags,
-    float* v_means3D, float* v_means2D_ndc, float* v_shs, float* v_shs_rest, float* v_colors_precomp, float* v_opacities,
-    float* v_scales, float* v_rotations, float* v_cov3D, void* stream, const gspl_bwd_adam_plan* plan) {
-    using namespace gspl;
+// cam: width and height come from the state; p.cov3d: the forward's
+static int rasterize_inria_bwd_impl(InriaParams p, const float* opacities, InriaCamera cam, const float* bg,
+                                    const int32_t* radii, const gspl_inria_state* st, const float* v_out_color,
+                                    float* packed /* [N, 9] scratch ([N, 10] with GSPL_INRIA_INVDEPTH) */, uint8_t* hit_flags,
+                                    const InriaGrads& v, void* stream, const gspl_bwd_adam_plan* plan) {
     if (!st || st->N < 0) return fail_arg("rasterize_inria_bwd: bad state");
-    const int N = st->N, width = st->width, height = st->height;
+    const int N = st->N;
     if (N == 0) return GSPL_OK;
-    if (!packed || !v_out_color || !v_means3D || !v_means2D_ndc || !v_opacities) return fail_arg("rasterize_inria_bwd: NULL required pointer");
-    const int tile = 16, tile_w = (width + 15) / 16, tile_h = (height + 15) / 16;
+    if (!packed || !v_out_color || !v.means || !v.means2d_ndc || !v.opacities) return fail_arg("rasterize_inria_bwd: NULL required pointer");
+    cam.width = st->width; cam.height = st->height;
+    p.cov3d = st->cov3d;
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipSuccess;
     const bool aa = (st->flags & GSPL_INRIA_ANTIALIAS) != 0, invd = (st->flags & GSPL_INRIA_INVDEPTH) != 0;
@@ -496,10 +484,9 @@ static int gspl::rasterize_inria_bwd_impl(
         e = hipMemsetAsync(hit_flags, 0, (size_t)N, s);
         if (e != hipSuccess) return check_hip(e, "rasterize_inria_bwd: clear");
     }
-    int rc = GSPL_OK;
     const bool raw = (st->flags & GSPL_INRIA_RAW_PARAMS) != 0;
     if (raw) {
-        if (!st->opacities || !v_scales || !v_rotations) return fail_arg("rasterize_inria_bwd: raw parameters need the forward's state, v_scales and v_rotations");
+        if (!st->opacities || !v.scales || !v.quats) return fail_arg("rasterize_inria_bwd: raw parameters need the forward's state, v_scales and v_rotations");
         opacities = st->opacities;         // the activated values the forward composited with
     }
     if (aa) {
@@ -515,14 +502,50 @@ static int gspl::rasterize_inria_bwd_impl(
         }
         if (!(st->flags & GSPL_INRIA_NO_SEGMENTS) && gspl_get_deterministic() == 0) seg.walk = seg_walk_words();      // plain or segmented: the walk lengths are left for the next forward
         ProfScope prof(1, s);
-        rc = composite_bwd_packed_impl(N, st->n_isects, D, GSPL_MODE_INRIA, GSPL_LAYOUT_CHW, st->means2d, st->conics, st->colors, opacities, bg, width,
-                                       height, tile, tile_w, tile_h, st->offsets, st->flatten_ids, st->final_Ts, st->last_ids, v_out_color, nullptr,
-                                       packed, prow, 0, hit_flags, s, &seg);
+        const int rc = composite_bwd_packed_impl(N, D, GSPL_MODE_INRIA, GSPL_LAYOUT_CHW, CompositeSplats{st->means2d, st->conics, st->colors, opacities, bg},
+                                                 ImageSize{cam.width, cam.height}, tile_grid16(cam.width, cam.height),
+                                                 TileLists{st->offsets, st->flatten_ids, st->n_isects}, st->final_Ts, st->last_ids, v_out_color, nullptr,
+                                                 packed, prow, 0, hit_flags, s, &seg);
         if (rc != GSPL_OK) return rc;
     }
-    return inria_preprocess_bwd_impl(N, degree, n_coeffs, means3D, scales, rotations, st->cov3d, shs, shs_rest, viewmatrix, projmatrix, campos, width, height,
-                                     tanfovx, tanfovy, scale_modifier, radii, st->clamped, packed, packed + 2, packed + 6, prow, v_means3D, v_scales,
-                                     v_rotations, v_cov3D, v_shs, v_shs_rest, v_colors_precomp, v_means2D_ndc, packed + 5, v_opacities, st->sh_jac,
+    return inria_preprocess_bwd_impl(N, p, cam, radii, st->clamped, SplatGradRows::packed(packed, prow), v, st->sh_jac,
                                      aa ? caller_opacities : (raw ? st->opacities : nullptr), s, plan, BwdStats{st->stats_accum, st->stats_denom, st->stats_max_radii},
                                      st->flags & (GSPL_INRIA_RAW_PARAMS | GSPL_INRIA_ANTIALIAS | GSPL_INRIA_INVDEPTH));
+}
+}  // namespace gspl
+
+extern "C" int gspl_rasterize_inria_bwd(
+    int degree, int n_coeffs,
+    const float* means3D, const float* scales, const float* rotations, const float* shs, const float* shs_rest, const float* opacities,
+    const float* viewmatrix, const float* projmatrix, const float* campos, const float* bg,
+    float tanfovx, float tanfovy, float scale_modifier,
+    const int32_t* radii, const gspl_inria_state* st, const float* v_out_color,
+    float* packed, uint8_t* hit_flags,
+    float* v_means3D, float* v_means2D_ndc, float* v_shs, float* v_shs_rest, float* v_colors_precomp, float* v_opacities,
+    float* v_scales, float* v_rotations, float* v_cov3D, void* stream) {
+    using namespace gspl;
+    return rasterize_inria_bwd_impl(InriaParams{means3D, scales, rotations, nullptr, shs, shs_rest, degree, n_coeffs}, opacities,
+                                    InriaCamera{viewmatrix, projmatrix, campos, 0, 0, tanfovx, tanfovy, scale_modifier}, bg, radii, st, v_out_color, packed, hit_flags,
+                                    InriaGrads{v_means3D, v_scales, v_rotations, v_cov3D, v_shs, v_shs_rest, v_colors_precomp, v_means2D_ndc, v_opacities}, stream, nullptr);
+}
+
+// The same backward with the optimizer INSIDE it (VERDICT r4 #2): the per-Gaussian kernels at the end of the backward (SH backward,
+// preprocess backward) apply the Adam update to the parameter rows they have just produced the gradient of, instead of writing
+// 236 B of gradient per Gaussian for a separate optimizer launch to read back.  The parameters are updated IN PLACE; only the
+// screen-space gradient (what the density controller reads, vanilla_density_controller.py:101-123) is written.
+extern "C" int gspl_rasterize_inria_bwd_adam(
+    int degree, int n_coeffs,
+    float* means3D, float* scales, float* rotations, float* shs, float* shs_rest, float* opacities,
+    const float* viewmatrix, const float* projmatrix, const float* campos, const float* bg,
+    float tanfovx, float tanfovy, float scale_modifier,
+    const int32_t* radii, const gspl_inria_state* st, const float* v_out_color,
+    float* packed, uint8_t* hit_flags, float* scratch_means, float* v_means2D_ndc, const gspl_bwd_adam_plan* plan, void* stream) {
+    using namespace gspl;
+    if (!plan) return fail_arg("rasterize_inria_bwd_adam: NULL plan");
+    if (!scales || !rotations || !shs || !opacities) return fail_arg("rasterize_inria_bwd_adam: needs scales, rotations, SH coefficients and opacities");
+    if (st && (st->flags & (GSPL_INRIA_ANTIALIAS | GSPL_INRIA_INVDEPTH)))
+        return fail_arg("rasterize_inria_bwd_adam: a frame rendered with GSPL_INRIA_ANTIALIAS or GSPL_INRIA_INVDEPTH takes gspl_rasterize_inria_bwd and a separate optimizer");
+    return rasterize_inria_bwd_impl(InriaParams{means3D, scales, rotations, nullptr, shs, shs_rest, degree, n_coeffs}, opacities,
+                                    InriaCamera{viewmatrix, projmatrix, campos, 0, 0, tanfovx, tanfovy, scale_modifier}, bg, radii, st, v_out_color, packed, hit_flags,
+                                    InriaGrads{scratch_means, scales, rotations, nullptr, shs, shs_rest, nullptr, v_means2D_ndc, opacities}, stream, plan);
 }

@@ -190,11 +190,11 @@ struct ListTiles {
     int w;         // list tiles per row
     int n;         // number of list tiles
 };
-static inline ListTiles list_tiles(int tile_size, int tile_w, int tile_h) {
+static inline ListTiles list_tiles(TileGrid grid) {
     ListTiles lt;
-    lt.log2 = tile_size == 8 ? 3 : (tile_size == 32 ? 5 : 4);
-    lt.w = tile_w;
-    lt.n = tile_w * tile_h;
+    lt.log2 = grid.size == 8 ? 3 : (grid.size == 32 ? 5 : 4);
+    lt.w = grid.w;
+    lt.n = grid.n();
     return lt;
 }
 __device__ __forceinline__ void block_list_range(const ListTiles& lt, int bx, int by, int width, int height, int64_t n_isects,
@@ -208,19 +208,20 @@ __device__ __forceinline__ void block_list_range(const ListTiles& lt, int bx, in
 // number of per-splat gradient values accumulated per (tile, splat): xy(2) conic(3) opacity(1) colour(D) [+abs xy(2)]
 template <int D, bool ABS> struct BwdVals { static constexpr int N = 6 + D + (ABS ? 2 : 0); };
 
-int check_composite_args(int N, int64_t n_isects, int D, int mode, int layout, int width, int height,
-                         int tile_size, int tile_w, int tile_h, const char* who);
+// argument groups of the compositing calls below the ABI (gspl_host.h has the tile grid): the splats as compositing reads them, the
+// image, and the per-tile lists (n_isects < 0: `offsets` has one more entry, the list length, left there by the device)
+struct CompositeSplats { const float* means2d; const float* conics; const float* colors; const float* opacities; const float* backgrounds; };
+struct ImageSize { int width, height; };
+struct TileLists { const int32_t* offsets; const int32_t* flatten_ids; int64_t n_isects; };
+
+int check_composite_args(int N, int64_t n_isects, int D, int mode, int layout, ImageSize image, TileGrid grid, const char* who);
 
 // gspl_composite_fwd / gspl_composite_bwd_packed with the segmentation state of the fused Inria call (fused.hip); seg == NULL: off
-int composite_fwd_impl(int N, int64_t n_isects, int D, int mode, int layout, const float* means2d, const float* conics, const float* colors,
-                       const float* opacities, const float* backgrounds, int width, int height, int tile_size, int tile_w, int tile_h,
-                       const int32_t* offsets, const int32_t* flatten_ids, float* out_colors, float* out_alphas, float* final_Ts, int32_t* last_ids,
-                       uint8_t* hit_flags, void* stream, const SegState* seg);
-int composite_bwd_packed_impl(int N, int64_t n_isects, int D, int mode, int layout, const float* means2d, const float* conics, const float* colors,
-                              const float* opacities, const float* backgrounds, int width, int height, int tile_size, int tile_w, int tile_h,
-                              const int32_t* offsets, const int32_t* flatten_ids, const float* final_Ts, const int32_t* last_ids,
-                              const float* v_out_colors, const float* v_out_alphas, float* v_packed, int packed_stride, int absgrad, uint8_t* hit_flags,
-                              void* stream, const SegState* seg);
+int composite_fwd_impl(int N, int D, int mode, int layout, const CompositeSplats& splats, ImageSize image, TileGrid grid, const TileLists& lists,
+                       float* out_colors, float* out_alphas, float* final_Ts, int32_t* last_ids, uint8_t* hit_flags, void* stream, const SegState* seg);
+int composite_bwd_packed_impl(int N, int D, int mode, int layout, const CompositeSplats& splats, ImageSize image, TileGrid grid, const TileLists& lists,
+                              const float* final_Ts, const int32_t* last_ids, const float* v_out_colors, const float* v_out_alphas,
+                              float* v_packed, int packed_stride, int absgrad, uint8_t* hit_flags, void* stream, const SegState* seg);
 
 // One launch of a kernel family templated on <D, MODE, CHW>: f(D, MODE, CHW) gets the three as std::integral_constants and returns the
 // call's code.  check_composite_args has refused every other mode and layout; a D outside {1, 2, 3, 4, 8} is GSPL_ERR_UNSUPPORTED.

@@ -438,11 +438,10 @@ int inria_invdepth_rows_launch(int N, const int32_t* radii, const float* colors3
 
 // geometry phase.  ext: GSPL_INRIA_RAW_PARAMS (the model's raw parameters; opacities_out [N] = sigmoid(raw_opacities)) and / or
 // GSPL_INRIA_ANTIALIAS (opacities_out = the effective opacities); with neither, the two opacity pointers are not looked at
-int inria_geometry_launch(int N, const float* means, const float* scales, const float* quats, const float* cov3d_precomp,
-                          const float* viewmatrix, const float* projmatrix, int width, int height, int tile_size,
-                          float tanfovx, float tanfovy, float scale_modifier,
+int inria_geometry_launch(int N, const InriaParams& p, const InriaCamera& cam, int tile_size,
                           int32_t* radii, float* means2d, float* depths, float* conics, float* cov3d,
                           const float* raw_opacities, float* opacities_out, hipStream_t s, ZeroJob zero, int ext) {
+    const float* cov3d_precomp = p.cov3d;
     const bool raw = (ext & GSPL_INRIA_RAW_PARAMS) != 0, aa = (ext & GSPL_INRIA_ANTIALIAS) != 0;
     // (`raw_opacities`: the caller's opacities, raw with GSPL_INRIA_RAW_PARAMS in `ext`, activated without)
     if (aa && (!raw_opacities || !opacities_out || (raw && cov3d_precomp)))
@@ -450,8 +449,8 @@ int inria_geometry_launch(int N, const float* means, const float* scales, const 
     if (raw && (cov3d_precomp || !raw_opacities || !opacities_out)) return fail_arg("inria_preprocess_fwd: raw parameters need scales + rotations and room for the opacities");
     dispatch_bools([&](auto R, auto AA) {
         hipLaunchKernelGGL((inria_preprocess_fwd_kernel<R(), AA()>), dim3((N + 255) / 256), dim3(256), 0, s,
-                           N, means, scales, quats, cov3d_precomp, viewmatrix, projmatrix, width, height, tile_size,
-                           tanfovx, tanfovy, scale_modifier, radii, means2d, depths, conics, cov3d, raw_opacities, opacities_out, zero.p, zero.n16);
+                           N, p.means, p.scales, p.quats, cov3d_precomp, cam.viewmatrix, cam.projmatrix, cam.width, cam.height, tile_size,
+                           cam.tanfovx, cam.tanfovy, cam.scale_modifier, radii, means2d, depths, conics, cov3d, raw_opacities, opacities_out, zero.p, zero.n16);
     }, raw, aa);
     return check_launch("inria_preprocess_fwd");
 }
@@ -479,8 +478,9 @@ extern "C" int gspl_inria_preprocess_fwd(int N, int degree, int n_coeffs,
     hipStream_t s = (hipStream_t)stream;
     const int grid = (N + 255) / 256;
     if (phases & GSPL_INRIA_GEOMETRY) {
-        int rc = inria_geometry_launch(N, means, scales, quats, cov3d_precomp, viewmatrix, projmatrix, width, height, tile_size, tanfovx, tanfovy,
-                                       scale_modifier, radii, means2d, depths, conics, cov3d, nullptr, nullptr, s);
+        int rc = inria_geometry_launch(N, InriaParams{means, scales, quats, cov3d_precomp, shs, shs_rest, degree, n_coeffs},
+                                       InriaCamera{viewmatrix, projmatrix, campos, width, height, tanfovx, tanfovy, scale_modifier}, tile_size,
+                                       radii, means2d, depths, conics, cov3d, nullptr, nullptr, s);
         if (rc != GSPL_OK) return rc;
     }
     if (!(phases & GSPL_INRIA_COLOURS)) return GSPL_OK;
@@ -490,27 +490,20 @@ extern "C" int gspl_inria_preprocess_fwd(int N, int degree, int n_coeffs,
     }
     // shs_rest == NULL: `shs` holds all n_coeffs rows of a Gaussian ([N, n_coeffs, 3]); otherwise `shs` is the DC row ([N, 1, 3]) and
     // `shs_rest` the others ([N, n_coeffs - 1, 3]) — the two parameters of the reference's model, read where they are
-    const int stride = 3 * n_coeffs;
-    if (shs_rest) return sh_fwd_launch(N, 1, degree, means, campos, shs, 3, shs_rest, stride - 3, nullptr, radii,
-                                       GSPL_SH_ADD_HALF_CLAMP, colors, clamped, stream, sh_jac);
-    return sh_fwd_launch(N, 1, degree, means, campos, shs, stride, shs + 3, stride, nullptr, radii,
-                         GSPL_SH_ADD_HALF_CLAMP, colors, clamped, stream, sh_jac);
+    return sh_fwd_launch(N, 1, degree, means, campos, sh_coeffs(shs, shs_rest, n_coeffs), nullptr, radii, GSPL_SH_ADD_HALF_CLAMP, colors, clamped, stream, sh_jac);
 }
 
 namespace gspl {
 // GSPL_INRIA_RAW_PARAMS in `ext`: scales / quats are RAW parameters (see inria_preprocess_fwd_kernel<true>) and opac_act the activated
 // opacities (with GSPL_INRIA_ANTIALIAS: the caller's opacities, raw or not)
-int inria_preprocess_bwd_impl(int N, int degree, int n_coeffs,
-                                         const float* means, const float* scales, const float* quats,
-                                         const float* cov3d, const float* shs, const float* shs_rest,
-                                         const float* viewmatrix, const float* projmatrix, const float* campos,
-                                         int width, int height, float tanfovx, float tanfovy, float scale_modifier,
-                                         const int32_t* radii, const uint8_t* clamped,
-                                         const float* v_means2d, const float* v_conics, const float* v_colors, int grad_stride,
-                                         float* v_means, float* v_scales, float* v_quats,
-                                         float* v_cov3d_precomp, float* v_shs, float* v_shs_rest, float* v_colors_precomp,
-                                         float* v_means2d_ndc, const float* v_opacities_packed, float* v_opacities, const float* sh_jac,
-                                         const float* opac_act, void* stream, const gspl_bwd_adam_plan* plan, BwdStats stats, int ext) {
+int inria_preprocess_bwd_impl(int N, const InriaParams& p, const InriaCamera& cam,
+                              const int32_t* radii, const uint8_t* clamped, const SplatGradRows& rows, const InriaGrads& v, const float* sh_jac,
+                              const float* opac_act, void* stream, const gspl_bwd_adam_plan* plan, BwdStats stats, int ext) {
+    const float *means = p.means, *scales = p.scales, *quats = p.quats, *cov3d = p.cov3d, *shs = p.shs, *shs_rest = p.shs_rest;
+    const int degree = p.degree, n_coeffs = p.n_coeffs, width = cam.width, height = cam.height, grad_stride = rows.stride;
+    const float *v_means2d = rows.xy, *v_conics = rows.conic, *v_colors = rows.colour, *v_opacities_packed = rows.opacity;
+    float *v_means = v.means, *v_scales = v.scales, *v_quats = v.quats, *v_cov3d_precomp = v.cov3d_precomp, *v_shs = v.shs, *v_shs_rest = v.shs_rest;
+    float *v_colors_precomp = v.colors_precomp, *v_means2d_ndc = v.means2d_ndc, *v_opacities = v.opacities;
     if (N < 0 || width <= 0 || height <= 0) return fail_arg("inria_preprocess_bwd: bad sizes");
     // ext: the fused call's GSPL_INRIA_RAW_PARAMS / GSPL_INRIA_ANTIALIAS / GSPL_INRIA_INVDEPTH bits
     if (ext & ~(GSPL_INRIA_RAW_PARAMS | GSPL_INRIA_ANTIALIAS | GSPL_INRIA_INVDEPTH)) return fail_arg("inria_preprocess_bwd: unknown extension bits");
@@ -534,7 +527,7 @@ int inria_preprocess_bwd_impl(int N, int degree, int n_coeffs,
     }
     if (v_opacities && (!v_opacities_packed || grad_stride <= 0)) return fail_arg("inria_preprocess_bwd: v_opacities needs the packed gradient buffer");
     if (N == 0) return GSPL_OK;
-    if (!means || !cov3d || !viewmatrix || !projmatrix || !radii || !v_means2d || !v_conics || !v_colors || !v_means || !v_means2d_ndc)
+    if (!means || !cov3d || !cam.viewmatrix || !cam.projmatrix || !radii || !v_means2d || !v_conics || !v_colors || !v_means || !v_means2d_ndc)
         return fail_arg("inria_preprocess_bwd: NULL required pointer");
     if ((v_scales == nullptr) != (v_quats == nullptr)) return fail_arg("inria_preprocess_bwd: v_scales and v_quats go together");
     if (v_scales && (!scales || !quats)) return fail_arg("inria_preprocess_bwd: scales/quats missing");
@@ -545,19 +538,15 @@ int inria_preprocess_bwd_impl(int N, int degree, int n_coeffs,
     const int gs2 = grad_stride > 0 ? grad_stride : 2, gs3 = grad_stride > 0 ? grad_stride : 3;
     bool accum = false;
     if (v_shs) {
-        if (!shs || !campos || !clamped) return fail_arg("inria_preprocess_bwd: shs/campos/clamped missing");
+        if (!shs || !cam.campos || !clamped) return fail_arg("inria_preprocess_bwd: shs/campos/clamped missing");
         if (degree < 0 || degree > 4 || n_coeffs < (degree + 1) * (degree + 1)) return fail_arg("inria_preprocess_bwd: bad degree / n_coeffs");
-        const int stride = 3 * n_coeffs;
         // dL/d(dir) lands in v_means; the geometry kernel accumulates on top
         if ((shs_rest == nullptr) != (v_shs_rest == nullptr)) return fail_arg("inria_preprocess_bwd: shs_rest and v_shs_rest go together");
         ShAdamHost sh_adam;
         if (plan) { sh_adam.dc = plan->shs; sh_adam.rest = shs_rest ? plan->shs_rest : plan->shs; }
         const ShAdamHost* sha = plan ? &sh_adam : nullptr;
-        int rc = shs_rest
-            ? sh_bwd_launch(N, 1, degree, n_coeffs, means, campos, shs, 3, shs_rest, stride - 3, nullptr, radii,
-                            GSPL_SH_ADD_HALF_CLAMP, clamped, v_colors, gs3, v_shs, v_shs_rest, v_means, stream, sh_jac, sha)
-            : sh_bwd_launch(N, 1, degree, n_coeffs, means, campos, shs, stride, shs + 3, stride, nullptr, radii,
-                            GSPL_SH_ADD_HALF_CLAMP, clamped, v_colors, gs3, v_shs, v_shs + 3, v_means, stream, sh_jac, sha);
+        int rc = sh_bwd_launch(N, 1, degree, n_coeffs, means, cam.campos, sh_coeffs(shs, shs_rest, n_coeffs), nullptr, radii,
+                               GSPL_SH_ADD_HALF_CLAMP, clamped, v_colors, gs3, sh_grads(v_shs, v_shs_rest), v_means, stream, sh_jac, sha);
         if (rc != GSPL_OK) return rc;
         accum = true;
     }
@@ -583,7 +572,7 @@ int inria_preprocess_bwd_impl(int N, int degree, int n_coeffs,
     dispatch_bools([&](auto A, auto R, auto AD, auto AAF, auto INVDF) {
         if constexpr (!AD() || (A() && !AAF() && !INVDF()))
             hipLaunchKernelGGL((inria_preprocess_bwd_kernel<A(), R(), AD(), AAF(), INVDF()>), dim3(grid), dim3(256), 0, s,
-                               N, means, scales, quats, cov3d, viewmatrix, projmatrix, width, height, tanfovx, tanfovy, scale_modifier,
+                               N, means, scales, quats, cov3d, cam.viewmatrix, cam.projmatrix, width, height, cam.tanfovx, cam.tanfovy, cam.scale_modifier,
                                radii, v_means2d, v_conics, gs2, gs3, v_means, v_scales, v_quats, v_cov3d_precomp, v_means2d_ndc, v_opacities_packed,
                                v_opacities, opac_act, pre, stats);
     }, accum, raw, plan != nullptr, aa, invd);
@@ -601,8 +590,10 @@ extern "C" int gspl_inria_preprocess_bwd(int N, int degree, int n_coeffs,
                                          float* v_means, float* v_scales, float* v_quats,
                                          float* v_cov3d_precomp, float* v_shs, float* v_shs_rest, float* v_colors_precomp,
                                          float* v_means2d_ndc, const float* v_opacities_packed, float* v_opacities, const float* sh_jac, void* stream) {
-    return gspl::inria_preprocess_bwd_impl(N, degree, n_coeffs, means, scales, quats, cov3d, shs, shs_rest, viewmatrix, projmatrix, campos, width, height,
-                                           tanfovx, tanfovy, scale_modifier, radii, clamped, v_means2d, v_conics, v_colors, grad_stride, v_means, v_scales,
-                                           v_quats, v_cov3d_precomp, v_shs, v_shs_rest, v_colors_precomp, v_means2d_ndc, v_opacities_packed, v_opacities,
-                                           sh_jac, nullptr, stream, nullptr, gspl::BwdStats(), 0);
+    using namespace gspl;
+    return inria_preprocess_bwd_impl(N, InriaParams{means, scales, quats, cov3d, shs, shs_rest, degree, n_coeffs},
+                                     InriaCamera{viewmatrix, projmatrix, campos, width, height, tanfovx, tanfovy, scale_modifier}, radii, clamped,
+                                     SplatGradRows{v_means2d, v_conics, v_colors, v_opacities_packed, grad_stride},
+                                     InriaGrads{v_means, v_scales, v_quats, v_cov3d_precomp, v_shs, v_shs_rest, v_colors_precomp, v_means2d_ndc, v_opacities},
+                                     sh_jac, nullptr, stream, nullptr, BwdStats(), 0);
 }

@@ -230,6 +230,14 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
     }
 }
 
+// A kernel templated on the camera model: f(CAM) gets GSPL_CAM_*_ as a std::integral_constant (the caller has refused every other model)
+template <class F>
+static void dispatch_camera(int camera_model, F&& f) {
+    if (camera_model == GSPL_CAMERA_ORTHO) f(std::integral_constant<int, GSPL_CAM_ORTHO_>{});
+    else if (camera_model == GSPL_CAMERA_FISHEYE) f(std::integral_constant<int, GSPL_CAM_FISHEYE_>{});
+    else f(std::integral_constant<int, GSPL_CAM_PINHOLE_>{});
+}
+
 }  // namespace gspl
 
 extern "C" int gspl_project_fwd(int C, int N,
@@ -248,14 +256,11 @@ extern "C" int gspl_project_fwd(int C, int N,
     const int64_t total = (int64_t)C * N;
     const int block = 256;
     const int64_t grid = (total + block - 1) / block;
-#define GSPL_PROJECT_FWD(CAM)                                                                                              \
-    hipLaunchKernelGGL(gspl::project_fwd_kernel<CAM>, dim3((unsigned)grid), dim3(block), 0, (hipStream_t)stream, C, N, means,   \
-                       scales, quats, viewmats, Ks, width, height, tile_size, scale_modifier, eps2d, near_plane, far_plane,   \
-                       radius_clip, radii, means2d, depths, conics, compensations, tiles_hit, cov3d)
-    if (camera_model == GSPL_CAMERA_ORTHO) GSPL_PROJECT_FWD(gspl::GSPL_CAM_ORTHO_);
-    else if (camera_model == GSPL_CAMERA_FISHEYE) GSPL_PROJECT_FWD(gspl::GSPL_CAM_FISHEYE_);
-    else GSPL_PROJECT_FWD(gspl::GSPL_CAM_PINHOLE_);
-#undef GSPL_PROJECT_FWD
+    gspl::dispatch_camera(camera_model, [&](auto cam) {
+        hipLaunchKernelGGL(gspl::project_fwd_kernel<cam()>, dim3((unsigned)grid), dim3(block), 0, (hipStream_t)stream, C, N, means,
+                           scales, quats, viewmats, Ks, width, height, tile_size, scale_modifier, eps2d, near_plane, far_plane,
+                           radius_clip, radii, means2d, depths, conics, compensations, tiles_hit, cov3d);
+    });
     return gspl::check_launch("project_fwd");
 }
 
@@ -279,15 +284,12 @@ extern "C" int gspl_project_bwd(int C, int N,
     const int64_t grid = (total + block - 1) / block;
     const int s2 = v_means2d_stride > 0 ? v_means2d_stride : 2, s3 = v_conics_stride > 0 ? v_conics_stride : 3;
     if ((s2 != 2 || s3 != 3) && C != 1) return gspl::fail_arg("project_bwd: strided gradients need C == 1");
-#define GSPL_PROJECT_BWD(ATOMIC, CAM)                                                                                      \
-    hipLaunchKernelGGL((gspl::project_bwd_kernel<ATOMIC, CAM>), dim3((unsigned)grid), dim3(block), 0, (hipStream_t)stream, C, N, \
-                       means, scales, quats, viewmats, Ks, width, height, scale_modifier, eps2d, radii, v_means2d, s2,        \
-                       v_depths, v_conics, s3, v_compensations, v_means, v_scales, v_quats)
-#define GSPL_PROJECT_BWD_CAM(CAM) do { if (C == 1) GSPL_PROJECT_BWD(false, CAM); else GSPL_PROJECT_BWD(true, CAM); } while (0)
-    if (camera_model == GSPL_CAMERA_ORTHO) GSPL_PROJECT_BWD_CAM(gspl::GSPL_CAM_ORTHO_);
-    else if (camera_model == GSPL_CAMERA_FISHEYE) GSPL_PROJECT_BWD_CAM(gspl::GSPL_CAM_FISHEYE_);
-    else GSPL_PROJECT_BWD_CAM(gspl::GSPL_CAM_PINHOLE_);
-#undef GSPL_PROJECT_BWD_CAM
-#undef GSPL_PROJECT_BWD
+    gspl::dispatch_camera(camera_model, [&](auto cam) {
+        gspl::dispatch_bools([&](auto one) {      // (several cameras add into the same rows)
+            hipLaunchKernelGGL((gspl::project_bwd_kernel<!one(), cam()>), dim3((unsigned)grid), dim3(block), 0, (hipStream_t)stream, C, N,
+                               means, scales, quats, viewmats, Ks, width, height, scale_modifier, eps2d, radii, v_means2d, s2,
+                               v_depths, v_conics, s3, v_compensations, v_means, v_scales, v_quats);
+        }, C == 1);
+    });
     return gspl::check_launch("project_bwd");
 }

@@ -106,23 +106,15 @@ __device__ __forceinline__ void sh_basis_grad(int degree, float x, float y, floa
     { const float c = 0.6258357354491761f * w[24]; gx += c * (4.f * xx * x - 12.f * x * yy); gy += c * (-12.f * xx * y + 4.f * yy * y); }
 }
 
-// The coefficient rows and their gradients are streamed once per launch: nontemporal accesses (-DGSPL_SH_PLAIN: plain ones).
+// The coefficient rows and their gradients are streamed once per launch: nontemporal accesses.
 typedef float sh_v4f __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 sh_load16(const float4* p) {
-#ifdef GSPL_SH_PLAIN
-    return *p;
-#else
     const sh_v4f t = __builtin_nontemporal_load(reinterpret_cast<const sh_v4f*>(p));
     return make_float4(t.x, t.y, t.z, t.w);
-#endif
 }
 __device__ __forceinline__ void sh_store16(float4* p, const float4& q) {
-#ifdef GSPL_SH_PLAIN
-    *p = q;
-#else
     const sh_v4f t = {q.x, q.y, q.z, q.w};
     __builtin_nontemporal_store(t, reinterpret_cast<sh_v4f*>(p));
-#endif
 }
 
 // Flat coalesced copy of `rows` rows x `rs` floats (contiguous in global) into LDS rows of stride ls.
@@ -485,11 +477,11 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 }  // namespace gspl
 
 namespace gspl {
-int sh_fwd_launch(int N, int C, int degree,
-                  const float* dirs, const float* origin,
-                  const float* dc, int dc_stride, const float* rest, int rest_stride,
+int sh_fwd_launch(int N, int C, int degree, const float* dirs, const float* origin, ShCoeffs sh,
                   const uint8_t* mask, const int32_t* mask32, int flags,
                   float* colors, uint8_t* clamped, void* stream, float* jac) {
+    const float *dc = sh.dc, *rest = sh.rest;
+    const int dc_stride = sh.dc_stride, rest_stride = sh.rest_stride;
     if (N < 0 || C < 1 || degree < 0 || degree > 4) return fail_arg("sh_fwd: bad N/C/degree");
     if (jac && C != 1) return fail_arg("sh_fwd: the direction Jacobian is kept for one camera only");
     if (C > 1 && !origin) return fail_arg("sh_fwd: several cameras need their origins");
@@ -527,7 +519,7 @@ extern "C" int gspl_sh_fwd(int N, int degree,
                            const float* dc, int dc_stride, const float* rest, int rest_stride,
                            const uint8_t* mask, int flags,
                            float* colors, uint8_t* clamped, void* stream) {
-    return gspl::sh_fwd_launch(N, 1, degree, dirs, origin, dc, dc_stride, rest, rest_stride, mask, nullptr, flags, colors, clamped, stream, nullptr);
+    return gspl::sh_fwd_launch(N, 1, degree, dirs, origin, gspl::ShCoeffs{dc, dc_stride, rest, rest_stride}, mask, nullptr, flags, colors, clamped, stream, nullptr);
 }
 
 // C cameras in one launch: origins [C,3], radii [C,N] (radius > 0 = evaluate; may be NULL), colors [C,N,3], clamped [C,N,3].
@@ -537,16 +529,16 @@ extern "C" int gspl_sh_fwd_batched(int C, int N, int degree,
                                    const float* dc, int dc_stride, const float* rest, int rest_stride,
                                    const int32_t* radii, int flags,
                                    float* colors, uint8_t* clamped, void* stream) {
-    return gspl::sh_fwd_launch(N, C, degree, means, origins, dc, dc_stride, rest, rest_stride, nullptr, radii, flags, colors, clamped, stream, nullptr);
+    return gspl::sh_fwd_launch(N, C, degree, means, origins, gspl::ShCoeffs{dc, dc_stride, rest, rest_stride}, nullptr, radii, flags, colors, clamped, stream, nullptr);
 }
 
 namespace gspl {
-int sh_bwd_launch(int N, int C, int degree, int n_coeffs,
-                  const float* dirs, const float* origin,
-                  const float* dc, int dc_stride, const float* rest, int rest_stride,
+int sh_bwd_launch(int N, int C, int degree, int n_coeffs, const float* dirs, const float* origin, ShCoeffs sh,
                   const uint8_t* mask, const int32_t* mask32, int flags, const uint8_t* clamped,
-                  const float* v_colors, int vc_stride,
-                  float* v_dc, float* v_rest, float* v_dirs, void* stream, const float* jac, const ShAdamHost* adam_host) {
+                  const float* v_colors, int vc_stride, ShGrads v_sh, float* v_dirs, void* stream, const float* jac, const ShAdamHost* adam_host) {
+    const float *dc = sh.dc, *rest = sh.rest;
+    const int dc_stride = sh.dc_stride, rest_stride = sh.rest_stride;
+    float *v_dc = v_sh.dc, *v_rest = v_sh.rest;
     if (N < 0 || C < 1 || degree < 0 || degree > 4 || n_coeffs < (degree + 1) * (degree + 1)) return fail_arg("sh_bwd: bad N/C/degree/n_coeffs");
     // adam_host: apply the Adam update instead of writing the coefficient gradients; v_dc / v_rest are then the PARAMETERS (the
     // layout is decided on them as it would be on the gradient arrays, which have the parameters' strides)
@@ -615,8 +607,8 @@ extern "C" int gspl_sh_bwd(int N, int degree, int n_coeffs,
                            const uint8_t* mask, int flags, const uint8_t* clamped,
                            const float* v_colors, int v_colors_stride,
                            float* v_dc, float* v_rest, float* v_dirs, void* stream) {
-    return gspl::sh_bwd_launch(N, 1, degree, n_coeffs, dirs, origin, dc, dc_stride, rest, rest_stride, mask, nullptr, flags, clamped, v_colors,
-                               v_colors_stride > 0 ? v_colors_stride : 3, v_dc, v_rest, v_dirs, stream, nullptr, nullptr);
+    return gspl::sh_bwd_launch(N, 1, degree, n_coeffs, dirs, origin, gspl::ShCoeffs{dc, dc_stride, rest, rest_stride}, mask, nullptr, flags, clamped, v_colors,
+                               v_colors_stride > 0 ? v_colors_stride : 3, gspl::ShGrads{v_dc, v_rest}, v_dirs, stream, nullptr, nullptr);
 }
 
 // Backward of gspl_sh_fwd_batched: v_colors [C,N,3] (dense) -> v_dc / v_rest summed over the cameras, written once.
@@ -625,6 +617,6 @@ extern "C" int gspl_sh_bwd_batched(int C, int N, int degree, int n_coeffs,
                                    int dc_stride, int rest_stride,
                                    const int32_t* radii, int flags, const uint8_t* clamped,
                                    const float* v_colors, float* v_dc, float* v_rest, void* stream) {
-    return gspl::sh_bwd_launch(N, C, degree, n_coeffs, means, origins, nullptr, dc_stride, nullptr, rest_stride, nullptr, radii, flags, clamped,
-                               v_colors, 3, v_dc, v_rest, nullptr, stream, nullptr, nullptr);
+    return gspl::sh_bwd_launch(N, C, degree, n_coeffs, means, origins, gspl::ShCoeffs{nullptr, dc_stride, nullptr, rest_stride}, nullptr, radii, flags, clamped,
+                               v_colors, 3, gspl::ShGrads{v_dc, v_rest}, nullptr, stream, nullptr, nullptr);
 }

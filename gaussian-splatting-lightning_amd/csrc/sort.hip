@@ -33,11 +33,7 @@ static constexpr int RS_THREADS = RS_WAVES * 64;
 // the keys and values of a pass are read once: streaming loads
 template <typename T>
 __device__ __forceinline__ T load_once(const T* p) {
-#ifdef GSPL_RS_PLAIN_LOAD
-    return *p;
-#else
     return __builtin_nontemporal_load(p);
-#endif
 }
 
 // Exclusive scan of 256 LDS words (src -> dst) by the first wave, four words per lane.
@@ -220,9 +216,7 @@ __global__ __launch_bounds__(RS_THREADS) void radix_scatter_kernel(const KeyT* _
 #pragma unroll
         for (int k = l; k < RADIX_BINS; k += 64) {
             sh.wcnt[w][k] = 0u;
-#ifndef GSPL_RS_MATCH_BALLOT
             sh.match[w][k] = 0ull;
-#endif
         }
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -230,21 +224,6 @@ __global__ __launch_bounds__(RS_THREADS) void radix_scatter_kernel(const KeyT* _
             const uint32_t slot = (uint32_t)(w * (64 * IPT) + r * 64 + l);
             const bool valid = slot < tile_n;
             const uint32_t d = (uint32_t)(key[r] >> shift) & mask;
-#ifdef GSPL_RS_MATCH_BALLOT
-            unsigned long long peers = __ballot(valid);
-            for (int b = 0; b < nbits; ++b) {
-                const bool bit = (d >> b) & 1u;
-                const unsigned long long bal = __ballot(valid && bit);
-                peers &= bit ? bal : ~bal;
-            }
-            const uint32_t cnt = (uint32_t)__builtin_popcountll(peers);
-            const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(peers >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)peers, 0u));
-            uint32_t old = 0u;
-            if (valid && below == 0u) { old = sh.wcnt[w][d]; sh.wcnt[w][d] = old + cnt; }
-            const int leader = valid ? (int)__builtin_ctzll(peers) : l;
-            old = __shfl(old, leader);
-            rk[r] = old + below;
-#else
             // A wave whose items all carry ONE digit (the top byte of depth keys: a handful of values for a whole frame) needs no
             // matching: the rank is the lane's position among the valid lanes.  64 lanes OR-ing into one LDS word serialise — the
             // last depth pass ran 40 % longer than the others (16.4 against 11.5 us at 1 M keys, 115 against 72 at 6 M).
@@ -275,7 +254,6 @@ __global__ __launch_bounds__(RS_THREADS) void radix_scatter_kernel(const KeyT* _
             }
             rk[r] = old + below;
             }
-#endif
             __builtin_amdgcn_wave_barrier();
         }
         __syncthreads();

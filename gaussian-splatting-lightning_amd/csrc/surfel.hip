@@ -476,6 +476,13 @@ static SurfelImageLayout surfel_image_layout(size_t pixels, size_t tiles) {
     return m;
 }
 
+static void carve_surfel_state(gspl_surfel_state* st, char* geom, const SurfelGeomLayout& g, char* img, const SurfelImageLayout& im) {
+    st->rec = (float*)(geom + g.rec); st->means2d = (float*)(geom + g.means2d); st->depths = (float*)(geom + g.depths);
+    st->colors = (float*)(geom + g.colors); st->clamped = (uint8_t*)(geom + g.clamped);
+    st->final_T = (float*)(img + im.final_T); st->M1 = (float*)(img + im.M1); st->M2 = (float*)(img + im.M2);
+    st->last_contrib = (int32_t*)(img + im.last); st->median_contrib = (int32_t*)(img + im.median); st->offsets = (int32_t*)(img + im.offsets);
+}
+
 }  // namespace gspl
 
 extern "C" size_t gspl_surfel_state_bytes(void) { return sizeof(gspl_surfel_state); }
@@ -492,7 +499,8 @@ extern "C" int gspl_rasterize_surfel_fwd(
     if (N > 0 && (!means3D || !scales || !rotations || !opacities || !radii || !viewmatrix || !projmatrix)) return fail_arg("rasterize_surfel_fwd: NULL required pointer");
     if (N > 0 && !colors_precomp && (!shs || !campos || degree < 0 || degree > 4 || n_coeffs < (degree + 1) * (degree + 1)))
         return fail_arg("rasterize_surfel_fwd: need shs + campos (and a valid degree / n_coeffs) or colors_precomp");
-    const int tile_w = (width + 15) / 16, tile_h = (height + 15) / 16, n_tiles = tile_w * tile_h;
+    const TileGrid grid = tile_grid16(width, height);
+    const int tile_w = grid.w, n_tiles = grid.n();
     hipStream_t s = (hipStream_t)stream;
     memset(st, 0, sizeof(*st));
     st->N = N; st->width = width; st->height = height;
@@ -502,10 +510,7 @@ extern "C" int gspl_rasterize_surfel_fwd(
     char* geom = (char*)alloc(alloc_ctx, GSPL_BUF_GEOMETRY, g.total);
     char* img = (char*)alloc(alloc_ctx, GSPL_BUF_IMAGE, im.total);
     if (!geom || !img) return fail_arg("rasterize_surfel_fwd: allocation call-back returned NULL");
-    st->rec = (float*)(geom + g.rec); st->means2d = (float*)(geom + g.means2d); st->depths = (float*)(geom + g.depths);
-    st->colors = (float*)(geom + g.colors); st->clamped = (uint8_t*)(geom + g.clamped);
-    st->final_T = (float*)(img + im.final_T); st->M1 = (float*)(img + im.M1); st->M2 = (float*)(img + im.M2);
-    st->last_contrib = (int32_t*)(img + im.last); st->median_contrib = (int32_t*)(img + im.median); st->offsets = (int32_t*)(img + im.offsets);
+    carve_surfel_state(st, geom, g, img, im);
     int64_t n_isects = 0;
     int rc = GSPL_OK;
     if (N > 0) {
@@ -514,8 +519,7 @@ extern "C" int gspl_rasterize_surfel_fwd(
         rc = check_launch("rasterize_surfel_fwd(preprocess)");
         if (rc != GSPL_OK) return rc;
         if (!colors_precomp) {
-            const int stride = 3 * n_coeffs;
-            rc = sh_fwd_launch(N, 1, degree, means3D, campos, shs, stride, shs + 3, stride, nullptr, radii, GSPL_SH_ADD_HALF_CLAMP, st->colors,
+            rc = sh_fwd_launch(N, 1, degree, means3D, campos, sh_coeffs(shs, nullptr, n_coeffs), nullptr, radii, GSPL_SH_ADD_HALF_CLAMP, st->colors,
                                st->clamped, stream, nullptr);
             if (rc != GSPL_OK) return rc;
         }
@@ -524,13 +528,10 @@ extern "C" int gspl_rasterize_surfel_fwd(
         int64_t* host = pinned_words();
         if (!ws1) return fail_arg("rasterize_surfel_fwd: allocation call-back returned NULL");
         if (!host) return fail_arg("rasterize_surfel_fwd: no pinned host word");
-        int32_t* order = (int32_t*)(geom + g.order);
-        int64_t* cum = (int64_t*)(geom + g.cum);
-        int32_t* big_list = (int32_t*)(geom + g.big_list);
-        void* spans = geom + g.spans;
+        const BinSplats bins{N, GSPL_MODE_INRIA, st->means2d, radii, st->depths, nullptr, nullptr};
+        const BinOrder ord{(int32_t*)(geom + g.order), (int64_t*)(geom + g.cum), (int32_t*)(geom + g.big_list), geom + g.spans};
         host[0] = -1;
-        rc = gspl_bin_count(N, GSPL_MODE_INRIA, st->means2d, radii, st->depths, nullptr, nullptr, 16, tile_w, tile_h, order, cum, big_list, spans,
-                            host, ws1, ws1_bytes, stream);
+        rc = bin_count_ticket(bins, grid, ord, host, ws1, ws1_bytes, stream, 0ull);
         // the frame's one read-back: the list length, stored into pinned memory by the scan (also waited for when the count failed: the
         // scan may be in flight, and `host` is the thread's one block)
         const int rc_sync = check_hip(hipStreamSynchronize(s), "rasterize_surfel_fwd: list length");
@@ -538,8 +539,7 @@ extern "C" int gspl_rasterize_surfel_fwd(
         if (rc_sync != GSPL_OK) return rc_sync;
         n_isects = host[0];
         if (n_isects < 0) return fail_arg("rasterize_surfel_fwd: the list length never arrived");
-        rc = bin_lists_known(N, GSPL_MODE_INRIA, st->means2d, radii, nullptr, nullptr, order, cum, big_list, spans, 16, tile_w, tile_h, n_isects,
-                             alloc, alloc_ctx, &st->flatten_ids, st->offsets, stream, "rasterize_surfel_fwd");
+        rc = bin_lists_known(bins, ord, grid, n_isects, alloc, alloc_ctx, &st->flatten_ids, st->offsets, stream, "rasterize_surfel_fwd");
         if (rc != GSPL_OK) return rc;
     }
     st->n_isects = n_isects;
@@ -593,9 +593,8 @@ extern "C" int gspl_rasterize_surfel_bwd(
     }
     bool accum = false;
     if (v_shs) {
-        const int stride = 3 * n_coeffs;
-        rc = sh_bwd_launch(N, 1, degree, n_coeffs, means3D, campos, shs, stride, shs + 3, stride, nullptr, radii, GSPL_SH_ADD_HALF_CLAMP, st->clamped,
-                           v_rows + 15, SURF_GRAD, v_shs, v_shs + 3, v_means3D, stream, nullptr, nullptr);
+        rc = sh_bwd_launch(N, 1, degree, n_coeffs, means3D, campos, sh_coeffs(shs, nullptr, n_coeffs), nullptr, radii, GSPL_SH_ADD_HALF_CLAMP, st->clamped,
+                           v_rows + 15, SURF_GRAD, sh_grads(v_shs, nullptr), v_means3D, stream, nullptr, nullptr);
         if (rc != GSPL_OK) return rc;
         accum = true;
     }
