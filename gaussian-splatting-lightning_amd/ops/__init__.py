@@ -17,6 +17,9 @@ reference's renderers call (same names, argument meaning and error behaviour):
       bilagrid_slice, bilagrid_tv
   Surface maps (internal/renderers/vanilla_2dgs_renderer.py:146-170, internal/metrics/gs2d_metrics.py, `gsplat.utils.depth_to_normal`)
       depth_to_normal, gsplat_rays, surfel_maps, surface_reg
+  Wide feature maps (internal/renderers/feature_3dgs_renderer.py, gsplat_contrastive_feature_renderer.py: `rasterize_gaussians` with
+  32 .. 512 channels over a frozen model)
+      rasterize_features
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -46,6 +49,7 @@ from .surfel import SurfelRasterizationSettings, SurfelGaussianRasterizer, raste
 from .mcmc import compute_relocation, perturb_means_, mcmc_regularization, mcmc_randn, _MCMCRegFn
 from .bilagrid import bilagrid_slice, bilagrid_tv, _SliceFn, _TvFn
 from .surface import depth_to_normal, gsplat_rays, surfel_maps, surface_reg, _DepthNormalFn, _SurfelMapsFn, _SurfaceRegFn
+from .features import rasterize_features, _FeatureFn
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

@@ -874,6 +874,35 @@ int gspl_surface_reg_fwd(int H, int W, const float* a, const float* b, const flo
 int gspl_surface_reg_bwd(int H, int W, const float* a, const float* b, const float* grad_out, float* v_a /*nullable*/,
                          float* v_b /*nullable*/, float* v_dist /*nullable*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 16. Wide-feature compositing (csrc/features.hip).  PURELY ADDITIVE: two new entry points, nothing existing changes,
+ *    GSPL_ABI_VERSION stays 39.  What Feature-3DGS (internal/renderers/feature_3dgs_renderer.py) and SegAnyGS
+ *    (internal/renderers/gsplat_contrastive_feature_renderer.py) ask of a rasterizer: many channels per splat composited over a
+ *    frozen model, and the gradient of the features alone.
+ *
+ *  Arguments as gspl_composite_fwd / gspl_composite_bwd (section 4) with these differences: any D >= 1; `features` [N,D];
+ *  backgrounds [D] (nullable = zero); no hit flags.  n_isects < 0: `offsets` has tile_w tile_h + 1 entries, the last one the list
+ *  length (gspl_bin_sort_device_count).  tile_size 8, 16 or 32 (else GSPL_ERR_UNSUPPORTED); D < 1, an unknown mode or layout, a
+ *  tile grid that does not cover the image or a NULL required pointer: GSPL_ERR_INVALID_ARG, nothing is launched.
+ *  gspl_feature_fwd: out ([H,W,D] in GSPL_LAYOUT_HWC, [D,H,W] in GSPL_LAYOUT_CHW), out_alphas, final_Ts, last_ids [H,W], every element
+ *      written.  Per channel, out = the fmaf chain over the pixel's list in list order plus T background: bit-for-bit what
+ *      gspl_composite_fwd gives for the same channel, and the same out_alphas / final_Ts / last_ids.  N == 0 or n_isects == 0: the
+ *      background everywhere, alpha 0, T 1, last_ids 0; the splat and list pointers are not read (may be NULL).
+ *  gspl_feature_bwd: v_features [N,D] += sum over pixels of (alpha T) v_out[pixel, :] — ZEROED BY THE CALLER, accumulated with fp32
+ *      atomics (one per 8x8 pixel block, splat and channel; the order of the additions is not fixed, results are not
+ *      bit-reproducible).  v_out in `layout`.  No other gradient is computed.  N == 0 or n_isects == 0: nothing is launched.
+ * ---------------------------------------------------------------------------------------- */
+int gspl_feature_fwd(int N, int64_t n_isects, int D, int mode, int layout,
+                     const float* means2d, const float* conics, const float* features, const float* opacities,
+                     const float* backgrounds /*nullable*/, int width, int height, int tile_size, int tile_w, int tile_h,
+                     const int32_t* offsets, const int32_t* flatten_ids,
+                     float* out, float* out_alphas, float* final_Ts, int32_t* last_ids, void* stream);
+int gspl_feature_bwd(int N, int64_t n_isects, int D, int mode, int layout,
+                     const float* means2d, const float* conics, const float* opacities,
+                     int width, int height, int tile_size, int tile_w, int tile_h,
+                     const int32_t* offsets, const int32_t* flatten_ids, const int32_t* last_ids,
+                     const float* v_out, float* v_features, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
