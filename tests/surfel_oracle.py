@@ -88,8 +88,9 @@ def _composite_tile(pre, ids, colors, opac, xs, ys):
     if ids.numel() == 0:
         P = xs.numel()
         z1, z3 = torch.zeros(P, dtype=dt), torch.zeros((P, 3), dtype=dt)
-        return dict(color=z3, T=torch.ones(P, dtype=dt), depth=z1, normal=z3, median=z1, dist=z1, flagged=torch.zeros(P, dtype=torch.bool),
-                    rows=ids)
+        zi, zb = torch.zeros(P, dtype=torch.int64), torch.zeros(P, dtype=torch.bool)
+        return dict(color=z3, T=torch.ones(P, dtype=dt), depth=z1, normal=z3, median=z1, dist=z1, flagged=zb, rows=ids,
+                    pairs_3d=0, pairs_lowpass=0, pairs_clamped=0, contributors=zi, last=zi, stopped=zb, first_clamped=zb, list_length=0)
     Tu, Tv, Tw = pre["Tu"][ids], pre["Tv"][ids], pre["Tw"][ids]
     cen, nrm, col, o = pre["centre"][ids], pre["normal"][ids], colors[ids], opac[ids]
     x, y = xs[:, None, None].to(dt), ys[:, None, None].to(dt)
@@ -148,6 +149,17 @@ def _composite_tile(pre, ids, colors, opac, xs, ys):
         fk |= vis & pre["cos_fragile"][ids][None]
         fl = fk.any(1)
         touched = fk.any(0)
+        # statistics of the composited (pixel, splat) pairs: which paths a scene reaches
+        pos = idx + 1
+        out["pairs_3d"] = int((comp & use3).sum())
+        out["pairs_lowpass"] = int((comp & ~use3).sum())
+        out["pairs_clamped"] = int((comp & (a_raw > 0.99)).sum())
+        out["contributors"] = comp.sum(1)
+        out["last"] = torch.where(comp, pos, torch.zeros_like(pos)).max(dim=1).values      # one past the last contributor's list position
+        out["stopped"] = stop.any(1)
+        first = torch.where(comp, idx, torch.full_like(idx, ac.shape[1])).min(dim=1).values
+        out["first_clamped"] = comp.any(1) & (a_raw.gather(1, first.clamp_max(ac.shape[1] - 1)[:, None])[:, 0] > 0.99)
+        out["list_length"] = int(ids.numel())
     out["flagged"] = fl
     out["rows"] = ids[touched]
     return out
@@ -156,7 +168,11 @@ def _composite_tile(pre, ids, colors, opac, xs, ys):
 def render(means, scales, quats, opacities, sh_coeffs, degree, viewmatrix, projmatrix, campos, width, height, background,
            scale_modifier=1.0, colors_precomp=None, proxy=None, pixels=None):
     """dict(render [3,H,W], allmap [7,H,W], radii [N], flagged [H,W] bool, means2d_scale [N,2] (Tw.z W/2, Tw.z H/2: the proxy's
-    factors), pre (the preprocess dict)).  `proxy`: (zu, zv) zero tensors [N] whose gradients give the densification proxy."""
+    factors), pre (the preprocess dict)).  `proxy`: (zu, zv) zero tensors [N] whose gradients give the densification proxy.
+    Statistics of the composited (pixel, splat) pairs, for tests that must know which paths a scene reaches: pairs_3d / pairs_lowpass /
+    pairs_clamped (counts: the ray-splat intersection, the screen-space low-pass, a raw alpha above 0.99), contributors [H,W] (per
+    pixel), last [H,W] (the position in the tile's list one past the last contributor; 0: none), stopped [H,W] (the pixel met the
+    transmittance stop), first_clamped [H,W] (the first contributor's raw alpha is above 0.99), list_lengths [tiles_y, tiles_x]."""
     dt = means.dtype
     pre = preprocess(means, scales, quats, viewmatrix, projmatrix, width, height, scale_modifier, proxy)
     mask = pre["mask"]
@@ -196,9 +212,18 @@ def render(means, scales, quats, opacities, sh_coeffs, degree, viewmatrix, projm
             parts.append((xs, ys, r))
     # assemble without in-place writes into leaves that need gradients
     flagged_rows = torch.zeros(means.shape[0], dtype=torch.bool)
+    stats = {k: 0 for k in ("pairs_3d", "pairs_lowpass", "pairs_clamped")}
+    per_pixel = {k: torch.zeros((height, width), dtype=t) for k, t in (("contributors", torch.int64), ("last", torch.int64), ("stopped", torch.bool),
+                                                                      ("first_clamped", torch.bool))}
+    list_lengths = torch.zeros((th, tw), dtype=torch.int64)
     for xs, ys, r in parts:
         flagged[ys, xs] = r["flagged"]
         flagged_rows[r["rows"]] = True
+        for k in stats:
+            stats[k] += r[k]
+        for k, img in per_pixel.items():
+            img[ys, xs] = r[k]
+        list_lengths[int(ys[0]) // 16, int(xs[0]) // 16] = r["list_length"]
     def assemble(fn, c):
         img = torch.zeros((c, height * width), dtype=dt)
         for xs, ys, r in parts:
@@ -214,7 +239,8 @@ def render(means, scales, quats, opacities, sh_coeffs, degree, viewmatrix, projm
     allmap = torch.cat([assemble(lambda r: r["depth"][None], 1), 1 - T, assemble(lambda r: r["normal"].T, 3),
                         assemble(lambda r: r["median"][None], 1), assemble(lambda r: r["dist"][None], 1)], dim=0)
     scale2 = torch.stack([pre["Tw"][:, 2] * width / 2, pre["Tw"][:, 2] * height / 2], dim=-1).detach()
-    return dict(render=color, allmap=allmap, radii=pre["radii"], flagged=flagged, flagged_rows=flagged_rows, means2d_scale=scale2, pre=pre, rgb=rgb)
+    return dict(render=color, allmap=allmap, radii=pre["radii"], flagged=flagged, flagged_rows=flagged_rows, means2d_scale=scale2, pre=pre, rgb=rgb,
+                list_lengths=list_lengths, **stats, **per_pixel)
 
 
 def render_with_grads(means, scales, quats, opacities, sh_coeffs, degree, viewmatrix, projmatrix, campos, width, height, background,
