@@ -12,6 +12,12 @@
 // HBM-bound: 28 B per updated element (p, g, m, v read; p, m, v written).  All tensors of the model go through one
 // launch (blockIdx.y = tensor); lanes handle 16-byte chunks of the flat [N * row] arrays, the row's visibility is looked
 // up per element (byte loads, cache resident).
+//
+// grad_rows (gspl_selective_adam_rows): one byte per row, 0 = every gradient of the row is zero (the sparse tail of the fused Inria
+// backward leaves it).  Every row is still updated — moments decay and parameters move with g = 0, as torch.optim.Adam has it — but a
+// 16-byte chunk whose rows all carry 0 does not LOAD its gradient: adam_elem runs on a zero that arrives as a kernel argument, the same
+// instructions on the same values.  Applied to tensors of at least GSPL_ADAM_ROWS_MIN floats per row, where whole cache lines of the
+// gradient go unread; the 1-4 float tensors touch most of their lines at any density and are read as always.
 #include "gspl_device.h"
 #include "gspl_host.h"
 
@@ -29,8 +35,13 @@ struct AdamBatchDev { AdamTensorDev t[GSPL_ADAM_MAX_TENSORS]; };
 
 // (adam_elem: gspl_device.h — shared with the backward kernels that apply the update themselves)
 
+#ifndef GSPL_ADAM_ROWS_MIN
+#define GSPL_ADAM_ROWS_MIN 32      // floats per row: one 128-byte line
+#endif
+template <bool ROWS>
 __global__ __launch_bounds__(256) void selective_adam_kernel(AdamBatchDev batch, int N, const uint8_t* __restrict__ visible,
-                                                             float b1, float b2, float eps, float inv_bc1, float inv_bc2) {
+                                                             float b1, float b2, float eps, float inv_bc1, float inv_bc2,
+                                                             const uint8_t* __restrict__ grad_rows, float zero) {
     const AdamTensorDev T = batch.t[blockIdx.y];
     const int64_t total = (int64_t)N * T.row;
     const float step = T.lr * inv_bc1;
@@ -41,6 +52,17 @@ __global__ __launch_bounds__(256) void selective_adam_kernel(AdamBatchDev batch,
     // two 16-byte chunks per thread and iteration (8 loads in flight) and streaming (nontemporal) accesses of everything that is
     // not read again before the next step: 302 -> 257 us at 1 M Gaussians (1.65 GB: 6.4 TB/s)
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    // the rows of a chunk with ONE division per chunk, a 32-bit one wherever the tensor has fewer than 2^31 elements (a chunk of 4
+    // floats of a row of >= 32 lies in one row or two)
+    const bool use_rows = ROWS && T.row >= GSPL_ADAM_ROWS_MIN;
+    const bool narrow = total < ((int64_t)1 << 31);
+    auto has_grad = [&](int64_t e) {
+        int64_t r0;
+        int rem;
+        if (narrow) { const uint32_t q = (uint32_t)e / (uint32_t)T.row; r0 = q; rem = (int)((uint32_t)e - q * (uint32_t)T.row); }
+        else { r0 = e / T.row; rem = (int)(e - r0 * T.row); }
+        return grad_rows[r0] != 0 || (rem + 3 >= T.row && grad_rows[r0 + 1] != 0);
+    };
     for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < nvec; i0 += 2 * stride) {
         float4 p[2], g[2], m[2], v[2];
         bool vis[2][4], any[2] = {false, false};
@@ -54,7 +76,8 @@ __global__ __launch_bounds__(256) void selective_adam_kernel(AdamBatchDev batch,
             }
             if (any[u]) {
                 p[u] = ntl(T.p, i);
-                g[u] = ntl(T.g, i);
+                if (!use_rows || has_grad(i << 2)) g[u] = ntl(T.g, i);
+                else g[u] = make_float4(zero, zero, zero, zero);
                 m[u] = ntl(T.m, i);
                 v[u] = ntl(T.v, i);
             }
@@ -94,6 +117,12 @@ extern "C" int gspl_selective_adam(int n_tensors, const gspl_adam_tensor* tensor
 extern "C" int gspl_selective_adam_limited(int n_tensors, const gspl_adam_tensor* tensors, int N, const uint8_t* visible,
                                            float beta1, float beta2, float eps, float bias_correction1, float bias_correction2_sqrt,
                                            int max_blocks, void* stream) {
+    return gspl_selective_adam_rows(n_tensors, tensors, N, visible, nullptr, beta1, beta2, eps, bias_correction1, bias_correction2_sqrt, max_blocks, stream);
+}
+
+extern "C" int gspl_selective_adam_rows(int n_tensors, const gspl_adam_tensor* tensors, int N, const uint8_t* visible, const uint8_t* grad_rows,
+                                        float beta1, float beta2, float eps, float bias_correction1, float bias_correction2_sqrt,
+                                        int max_blocks, void* stream) {
     using namespace gspl;
     if (max_blocks < 0) return fail_arg("selective_adam: bad sizes");
     if (n_tensors < 0 || n_tensors > GSPL_ADAM_MAX_TENSORS || N < 0) return fail_arg("selective_adam: bad sizes");
@@ -115,7 +144,11 @@ extern "C" int gspl_selective_adam_limited(int n_tensors, const gspl_adam_tensor
     // max_blocks > 0: a launch that runs NEXT TO other work (the deferred update on the colour stream) keeps to that many workgroups
     // per tensor, so that it leaves wave slots on every CU to the kernels of the other stream; the loop is grid-strided either way
     const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(want, max_blocks > 0 ? max_blocks : 16384));
-    hipLaunchKernelGGL(selective_adam_kernel, dim3(gx, n_tensors), dim3(256), 0, (hipStream_t)stream, b, N, visible,
-                       beta1, beta2, eps, 1.f / bias_correction1, 1.f / bias_correction2_sqrt);
+    if (grad_rows)
+        hipLaunchKernelGGL(selective_adam_kernel<true>, dim3(gx, n_tensors), dim3(256), 0, (hipStream_t)stream, b, N, visible,
+                           beta1, beta2, eps, 1.f / bias_correction1, 1.f / bias_correction2_sqrt, grad_rows, 0.f);
+    else
+        hipLaunchKernelGGL(selective_adam_kernel<false>, dim3(gx, n_tensors), dim3(256), 0, (hipStream_t)stream, b, N, visible,
+                           beta1, beta2, eps, 1.f / bias_correction1, 1.f / bias_correction2_sqrt, nullptr, 0.f);
     return check_launch("selective_adam");
 }

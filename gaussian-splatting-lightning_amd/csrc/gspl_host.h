@@ -134,7 +134,8 @@ int sh_bwd_launch(int N, int C, int degree, int n_coeffs, const float* dirs, con
                   const uint8_t* mask, const int32_t* mask32, int flags, const uint8_t* clamped,
                   const float* v_colors, int vc_stride, ShGrads v_sh, float* v_dirs, void* stream,
                   const float* jac /* nullable: the forward's Jacobian; v_dirs then needs no coefficient read */,
-                  const ShAdamHost* adam /* nullable; not NULL: v_sh holds the PARAMETERS, updated in place, no gradient is written */);
+                  const ShAdamHost* adam /* nullable; not NULL: v_sh holds the PARAMETERS, updated in place, no gradient is written */,
+                  bool prezeroed = false /* v_sh and v_dirs are cleared already: only rows with a non-zero colour gradient are written (one camera) */);
 // A table that one kernel clears on behalf of a LATER kernel of the same stream (the tables of a prepared sort): the ~5 us
 // radix_zero launch in front of that kernel goes away (profiles/r09_sequence.txt has the two of a frame).  16-byte units.
 struct ZeroJob { uint4* p = nullptr; uint32_t n16 = 0; };
@@ -169,5 +170,7 @@ int inria_preprocess_bwd_impl(int N, const InriaParams& p, const InriaCamera& ca
                               const gspl_bwd_adam_plan* adam = nullptr /* not NULL: v.shs / v.shs_rest / v.scales / v.quats / v.opacities are
                               the PARAMETERS (as means, scales, quats are), updated in place; v.means is scratch [N,3] */,
                               BwdStats stats = BwdStats(),
-                              int ext = 0 /* GSPL_INRIA_RAW_PARAMS / GSPL_INRIA_ANTIALIAS / GSPL_INRIA_INVDEPTH: see inria.hip */);
+                              int ext = 0 /* GSPL_INRIA_RAW_PARAMS / GSPL_INRIA_ANTIALIAS / GSPL_INRIA_INVDEPTH: see inria.hip */,
+                              uint8_t* grad_rows = nullptr /* [N], not NULL: every array of `v` is CLEARED already; rows whose packed gradient is
+                              all zero are left alone, and grad_rows says which rows were written (inria.hip, PREZEROED) */);
 }  // namespace gspl

@@ -264,7 +264,14 @@ __device__ __forceinline__ void pre_adam_pass(const AdamTarget& T, int64_t base,
         gp[e] = p; gm[e] = m; gv[e] = v;
     }
 }
-template <bool ACCUM, bool RAW, bool ADAM = false, bool AA = false, bool INVD = false>
+// PREZEROED (never with ADAM; the fused backward's sparse tail, fused.hip): every output array was cleared before the launch and the
+// gradients come as packed rows (gs2 == gs3, v_means2d = the row's first column).  A row whose packed row is zero in all its columns
+// — nine in ten of a saturated frame — gets its densification statistics and nothing else: no geometry is read, nothing is written
+// (the dense form writes +-0 there, equal as values).  Every other row runs the code below unchanged — after the block's rows with a
+// gradient have been handed to its first threads, in row order: one wave in four then walks the long chain of dependent loads, not all
+// four with a few lanes each.  grad_rows[g] = 1 for the rows that were written, 0 for the others: the optimizer's licence not to read
+// their gradient (adam.hip).  The SH backward's rows are among the 1s: its colour gradient is three columns of the same packed row.
+template <bool ACCUM, bool RAW, bool ADAM = false, bool AA = false, bool INVD = false, bool PREZEROED = false>
 __global__ __launch_bounds__(256) void inria_preprocess_bwd_kernel(
     int N,
     const float* means, const float* scales, const float* quats,
@@ -275,15 +282,51 @@ __global__ __launch_bounds__(256) void inria_preprocess_bwd_kernel(
     const float* __restrict__ v_means2d, const float* __restrict__ v_conics, int gs2, int gs3,
     float* __restrict__ v_means, float* __restrict__ v_scales, float* __restrict__ v_quats,
     float* __restrict__ v_cov3d_precomp, float* __restrict__ v_means2d_ndc,
-    const float* __restrict__ v_opac_src, float* __restrict__ v_opac_dst, const float* __restrict__ opac_act, PreAdam adam, BwdStats stats) {
+    const float* __restrict__ v_opac_src, float* __restrict__ v_opac_dst, const float* __restrict__ opac_act, PreAdam adam, BwdStats stats,
+    uint8_t* __restrict__ grad_rows) {
     // ADAM: the block's 256 rows of gradients meet in LDS and the update runs as FLAT, coalesced 16-byte passes over the block's
     // slice of every array (pre_adam_pass) — a lane-per-row update reads and writes 33 strided dwords per Gaussian three times over
     // (95 us at 1 M, 527 us at 6 M: 3 TB/s); every thread of the block stays for the barrier, rows past N carry nothing.
     __shared__ __attribute__((aligned(16))) float s_grad[ADAM ? 256 * 11 : 4];      // means 768 | scales 768 | quats 1024 | opacities 256
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (!ADAM && g >= N) return;
-    const bool row = g < N;
+    int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (!ADAM && !PREZEROED && g >= N) return;
     static_assert(!(ADAM && (AA || INVD)), "the optimizer inside the backward takes neither anti-aliasing nor inverse depth");
+    static_assert(!(ADAM && PREZEROED), "the optimizer inside the backward writes no gradient rows");
+    if constexpr (PREZEROED) {
+        __shared__ int s_rows[256], s_wave[4];
+        bool nz = false;
+        if (g < N) {
+            // everything a row without a gradient needs, asked for at once: the kernel runs at the length of its chains of dependent
+            // loads (two rounds of waves, four round trips each in the dense form), not at the memory's speed
+            const float* prow = v_means2d + (int64_t)g * gs2;
+            float pv[INVD ? 10 : 9];
+#pragma unroll
+            for (int k = 0; k < (INVD ? 10 : 9); ++k) pv[k] = prow[k];
+            const int32_t radius = radii[g];
+            const float denom = stats.accum ? stats.denom[g] : 0.f;
+            const float max_radius = (stats.accum && stats.max_radii) ? stats.max_radii[g] : 0.f;
+#pragma unroll
+            for (int k = 0; k < (INVD ? 10 : 9); ++k) nz = nz || pv[k] != 0.f;
+            grad_rows[g] = nz ? 1 : 0;
+            // the statistics of a visible row whose screen-space gradient is zero: accum += 0, the other two as below
+            if (!nz && stats.accum && radius > 0) {
+                stats.denom[g] = denom + 1.f;
+                if (stats.max_radii) stats.max_radii[g] = fmaxf(max_radius, (float)radius);
+            }
+        }
+        const unsigned long long mine = __ballot(nz);
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if (lane == 0) s_wave[wave] = __popcll(mine);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { before += k < wave ? s_wave[k] : 0; total += s_wave[k]; }
+        if (nz) s_rows[before + __popcll(mine & ((1ull << lane) - 1ull))] = g;
+        __syncthreads();
+        if ((int)threadIdx.x >= total) return;
+        g = s_rows[threadIdx.x];
+    }
+    const bool row = g < N;
     float aa_g = 0.f, aa_o = 0.f, aa_comp = 1.f;
     if constexpr (AA) { aa_g = v_opac_src[(int64_t)g * gs2]; aa_o = RAW ? act_sigmoid(opac_act[g]) : opac_act[g]; }
     if (!AA && (ADAM || v_opac_dst)) {
@@ -498,7 +541,7 @@ namespace gspl {
 // opacities (with GSPL_INRIA_ANTIALIAS: the caller's opacities, raw or not)
 int inria_preprocess_bwd_impl(int N, const InriaParams& p, const InriaCamera& cam,
                               const int32_t* radii, const uint8_t* clamped, const SplatGradRows& rows, const InriaGrads& v, const float* sh_jac,
-                              const float* opac_act, void* stream, const gspl_bwd_adam_plan* plan, BwdStats stats, int ext) {
+                              const float* opac_act, void* stream, const gspl_bwd_adam_plan* plan, BwdStats stats, int ext, uint8_t* grad_rows) {
     const float *means = p.means, *scales = p.scales, *quats = p.quats, *cov3d = p.cov3d, *shs = p.shs, *shs_rest = p.shs_rest;
     const int degree = p.degree, n_coeffs = p.n_coeffs, width = cam.width, height = cam.height, grad_stride = rows.stride;
     const float *v_means2d = rows.xy, *v_conics = rows.conic, *v_colors = rows.colour, *v_opacities_packed = rows.opacity;
@@ -526,6 +569,10 @@ int inria_preprocess_bwd_impl(int N, const InriaParams& p, const InriaCamera& ca
         }
     }
     if (v_opacities && (!v_opacities_packed || grad_stride <= 0)) return fail_arg("inria_preprocess_bwd: v_opacities needs the packed gradient buffer");
+    // grad_rows: the form for cleared outputs; its zero test reads the packed row from its first column
+    if (grad_rows && (plan || grad_stride < ((ext & GSPL_INRIA_INVDEPTH) ? 10 : 9) || v_conics != v_means2d + 2 || v_colors != v_means2d + 6 ||
+                      v_opacities_packed != v_means2d + 5))
+        return fail_arg("inria_preprocess_bwd: grad_rows needs the packed gradient rows and no optimizer plan");
     if (N == 0) return GSPL_OK;
     if (!means || !cov3d || !cam.viewmatrix || !cam.projmatrix || !radii || !v_means2d || !v_conics || !v_colors || !v_means || !v_means2d_ndc)
         return fail_arg("inria_preprocess_bwd: NULL required pointer");
@@ -546,7 +593,7 @@ int inria_preprocess_bwd_impl(int N, const InriaParams& p, const InriaCamera& ca
         if (plan) { sh_adam.dc = plan->shs; sh_adam.rest = shs_rest ? plan->shs_rest : plan->shs; }
         const ShAdamHost* sha = plan ? &sh_adam : nullptr;
         int rc = sh_bwd_launch(N, 1, degree, n_coeffs, means, cam.campos, sh_coeffs(shs, shs_rest, n_coeffs), nullptr, radii,
-                               GSPL_SH_ADD_HALF_CLAMP, clamped, v_colors, gs3, sh_grads(v_shs, v_shs_rest), v_means, stream, sh_jac, sha);
+                               GSPL_SH_ADD_HALF_CLAMP, clamped, v_colors, gs3, sh_grads(v_shs, v_shs_rest), v_means, stream, sh_jac, sha, grad_rows != nullptr);
         if (rc != GSPL_OK) return rc;
         accum = true;
     }
@@ -568,14 +615,14 @@ int inria_preprocess_bwd_impl(int N, const InriaParams& p, const InriaCamera& ca
         pre.quats = target(v_quats, plan->rotations);
         pre.opac = target(v_opacities, plan->opacities);
     }
-    // ADAM goes with neither AA nor INVD (refused above) and always accumulates (it needs v_shs): the other combinations do not exist
-    dispatch_bools([&](auto A, auto R, auto AD, auto AAF, auto INVDF) {
-        if constexpr (!AD() || (A() && !AAF() && !INVDF()))
-            hipLaunchKernelGGL((inria_preprocess_bwd_kernel<A(), R(), AD(), AAF(), INVDF()>), dim3(grid), dim3(256), 0, s,
+    // ADAM goes with neither AA nor INVD nor grad_rows (refused above) and always accumulates (it needs v_shs): the other combinations do not exist
+    dispatch_bools([&](auto A, auto R, auto AD, auto AAF, auto INVDF, auto PZ) {
+        if constexpr (!AD() || (A() && !AAF() && !INVDF() && !PZ()))
+            hipLaunchKernelGGL((inria_preprocess_bwd_kernel<A(), R(), AD(), AAF(), INVDF(), PZ()>), dim3(grid), dim3(256), 0, s,
                                N, means, scales, quats, cov3d, cam.viewmatrix, cam.projmatrix, width, height, cam.tanfovx, cam.tanfovy, cam.scale_modifier,
                                radii, v_means2d, v_conics, gs2, gs3, v_means, v_scales, v_quats, v_cov3d_precomp, v_means2d_ndc, v_opacities_packed,
-                               v_opacities, opac_act, pre, stats);
-    }, accum, raw, plan != nullptr, aa, invd);
+                               v_opacities, opac_act, pre, stats, grad_rows);
+    }, accum, raw, plan != nullptr, aa, invd, grad_rows != nullptr);
     return check_launch("inria_preprocess_bwd");
 }
 }  // namespace gspl
@@ -595,5 +642,5 @@ extern "C" int gspl_inria_preprocess_bwd(int N, int degree, int n_coeffs,
                                      InriaCamera{viewmatrix, projmatrix, campos, width, height, tanfovx, tanfovy, scale_modifier}, radii, clamped,
                                      SplatGradRows{v_means2d, v_conics, v_colors, v_opacities_packed, grad_stride},
                                      InriaGrads{v_means, v_scales, v_quats, v_cov3d_precomp, v_shs, v_shs_rest, v_colors_precomp, v_means2d_ndc, v_opacities},
-                                     sh_jac, nullptr, stream, nullptr, BwdStats(), 0);
+                                     sh_jac, nullptr, stream, nullptr, BwdStats(), 0, nullptr);
 }

@@ -328,7 +328,11 @@ __global__ __launch_bounds__(SH_BLOCK) void sh_fwd_kernel(
 // WITH_DIRS: also produce v_dirs (needs the coefficients -> stages them first).
 // ADAM: the coefficient gradients are not written: the kernel applies the Adam update to the coefficient rows it has just produced the
 // gradient of (tile_adam; v_dc / v_rest are then only consulted for the layout, `adam` carries parameter, moments and hyper-parameters).
-template <int DEG, bool WITH_DIRS, bool ADAM = false>
+// PREZEROED (one camera, WITH_DIRS, never ADAM; the fused backward's sparse tail): v_dc / v_rest / v_dirs were cleared before the launch.
+// A row whose masked and clamp-masked colour gradient is zero in all three channels produces nothing — no direction read, no basis, no
+// store (the dense form writes +-0 there) — and the rows that remain are stored one by one from LDS, each by the wave that staged it,
+// instead of with the flat tile_store of the block's 256 rows.
+template <int DEG, bool WITH_DIRS, bool ADAM = false, bool PREZEROED = false>
 __global__ __launch_bounds__(SH_BLOCK) void sh_bwd_kernel(
     int N, int C, int n_coeffs,
     const float* __restrict__ dirs, const float* __restrict__ origin,
@@ -363,6 +367,9 @@ __global__ __launch_bounds__(SH_BLOCK) void sh_bwd_kernel(
                 vc[c] = v_colors[cn * vc_stride + c];
                 if ((flags & GSPL_SH_ADD_HALF_CLAMP) && clamped && clamped[cn * 3 + c]) vc[c] = 0.f;
             }
+            if constexpr (PREZEROED) live = vc[0] != 0.f || vc[1] != 0.f || vc[2] != 0.f;
+        }
+        if (live) {
             dx = dirs[n * 3 + 0]; dy = dirs[n * 3 + 1]; dz = dirs[n * 3 + 2];
             if (origin) { dx -= origin[cam * 3 + 0]; dy -= origin[cam * 3 + 1]; dz -= origin[cam * 3 + 2]; }
             inv = rsqrtf(dx * dx + dy * dy + dz * dz);
@@ -386,7 +393,7 @@ __global__ __launch_bounds__(SH_BLOCK) void sh_bwd_kernel(
                 const float dot = gx * dx + gy * dy + gz * dz;
                 g[0] = (gx - dx * dot) * inv; g[1] = (gy - dy * dot) * inv; g[2] = (gz - dz * dot) * inv;
             }
-            v_dirs[n * 3 + 0] = g[0]; v_dirs[n * 3 + 1] = g[1]; v_dirs[n * 3 + 2] = g[2];
+            if (!PREZEROED || live) { v_dirs[n * 3 + 0] = g[0]; v_dirs[n * 3 + 1] = g[1]; v_dirs[n * 3 + 2] = g[2]; }
         }
     } else if (WITH_DIRS) {      // one camera only (checked by the launcher)
         if (degree > 0) {
@@ -409,13 +416,13 @@ __global__ __launch_bounds__(SH_BLOCK) void sh_bwd_kernel(
                 const float dot = gx * dx + gy * dy + gz * dz;
                 g[0] = (gx - dx * dot) * inv; g[1] = (gy - dy * dot) * inv; g[2] = (gz - dz * dot) * inv;
             }
-            v_dirs[n * 3 + 0] = g[0]; v_dirs[n * 3 + 1] = g[1]; v_dirs[n * 3 + 2] = g[2];
+            if (!PREZEROED || live) { v_dirs[n * 3 + 0] = g[0]; v_dirs[n * 3 + 1] = g[1]; v_dirs[n * 3 + 2] = g[2]; }
         }
         __syncthreads();   // everyone is done reading the staged coefficients
     }
 
     // coefficient gradients: write own row into LDS (summed over the cameras), then one flat coalesced store
-    if (r < rows) {
+    if (r < rows && (!PREZEROED || live)) {
         float d0[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) d0[c] = live ? b[0] * vc[c] : 0.f;
@@ -467,7 +474,19 @@ __global__ __launch_bounds__(SH_BLOCK) void sh_bwd_kernel(
             tile_adam(adam.tile, (int64_t)n0 * tile.rs, rows, tile.rs, tile.ls, 1.f / (float)tile.rs, lds, vec_ok_out != 0);
         } else {
             float* base = tile.merged ? v_dc + (int64_t)n0 * tile.rs : v_rest + (int64_t)n0 * tile.rs;
-            tile_store(base, rows, tile.rs, tile.ls, 1.f / (float)tile.rs, lds, vec_ok_out != 0);
+            if constexpr (PREZEROED) {
+                // lane r staged row r: a wave's ballot names the rows it has to store, 64 consecutive floats per store instruction
+                static_assert(SH_BLOCK % 64 == 0, "a wave stores the rows its own lanes staged");
+                unsigned long long todo = __ballot(r < rows && live);
+                const int lane = r & 63, first = r - lane;
+                while (todo) {
+                    const int row = first + __builtin_ctzll(todo);
+                    todo &= todo - 1;
+                    for (int c = lane; c < tile.rs; c += 64) base[(int64_t)row * tile.rs + c] = lds[row * tile.ls + c];
+                }
+            } else {
+                tile_store(base, rows, tile.rs, tile.ls, 1.f / (float)tile.rs, lds, vec_ok_out != 0);
+            }
         }
     }
 }
@@ -535,7 +554,8 @@ extern "C" int gspl_sh_fwd_batched(int C, int N, int degree,
 namespace gspl {
 int sh_bwd_launch(int N, int C, int degree, int n_coeffs, const float* dirs, const float* origin, ShCoeffs sh,
                   const uint8_t* mask, const int32_t* mask32, int flags, const uint8_t* clamped,
-                  const float* v_colors, int vc_stride, ShGrads v_sh, float* v_dirs, void* stream, const float* jac, const ShAdamHost* adam_host) {
+                  const float* v_colors, int vc_stride, ShGrads v_sh, float* v_dirs, void* stream, const float* jac, const ShAdamHost* adam_host,
+                  bool prezeroed) {
     const float *dc = sh.dc, *rest = sh.rest;
     const int dc_stride = sh.dc_stride, rest_stride = sh.rest_stride;
     float *v_dc = v_sh.dc, *v_rest = v_sh.rest;
@@ -548,6 +568,7 @@ int sh_bwd_launch(int N, int C, int degree, int n_coeffs, const float* dirs, con
         if (!v_dc || !adam_host->dc.exp_avg || !adam_host->dc.exp_avg_sq || (n_coeffs > 1 && (!v_rest || !adam_host->rest.exp_avg || !adam_host->rest.exp_avg_sq)))
             return fail_arg("sh_bwd: Adam targets missing");
     }
+    if (prezeroed && (adam_host || C != 1 || !v_dirs)) return fail_arg("sh_bwd: the form for cleared outputs is the one-camera backward with the direction gradient and no optimizer");
     if (jac && !v_dirs) jac = nullptr;
     if (C > 1 && (v_dirs || !origin)) return fail_arg("sh_bwd: several cameras need their origins and give no direction gradient");
     if (N == 0) return GSPL_OK;
@@ -580,20 +601,21 @@ int sh_bwd_launch(int N, int C, int degree, int n_coeffs, const float* dirs, con
     const size_t lds_bytes = n_coeffs > 1 ? (size_t)SH_BLOCK * tile.ls * sizeof(float) : 0;
     if (lds_bytes > 160 * 1024) return fail_arg("sh_bwd: coefficient row too long for LDS staging");
     const int grid = (N + SH_BLOCK - 1) / SH_BLOCK;
-#define GSPL_SH_BWD(DEG, WD, AD)                                                                                      \
+#define GSPL_SH_BWD(DEG, WD, AD, PZ)                                                                                  \
     {                                                                                                                 \
         if (lds_bytes > 64 * 1024) {                                                                                  \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sh_bwd_kernel<DEG, WD, AD>),             \
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sh_bwd_kernel<DEG, WD, AD, PZ>),             \
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);           \
             if (e != hipSuccess) return check_hip(e, "sh_bwd: hipFuncSetAttribute");                                  \
         }                                                                                                             \
-        hipLaunchKernelGGL((sh_bwd_kernel<DEG, WD, AD>), dim3(grid), dim3(SH_BLOCK), lds_bytes, (hipStream_t)stream, N, C, \
+        hipLaunchKernelGGL((sh_bwd_kernel<DEG, WD, AD, PZ>), dim3(grid), dim3(SH_BLOCK), lds_bytes, (hipStream_t)stream, N, C, \
                            n_coeffs, dirs, origin, dc, dc_stride, rest, mask, mask32, flags, clamped, v_colors, vc_stride, tile, vec_in, \
                            vec_out, v_dc, v_rest, v_dirs, jac, adam);                                                 \
     }
 #define GSPL_SH_BWD_CASE(DEG) \
     case DEG:                 \
-        if (adam_host) GSPL_SH_BWD(DEG, true, true) else if (v_dirs) GSPL_SH_BWD(DEG, true, false) else GSPL_SH_BWD(DEG, false, false) break;
+        if (adam_host) GSPL_SH_BWD(DEG, true, true, false) else if (prezeroed) GSPL_SH_BWD(DEG, true, false, true)       \
+        else if (v_dirs) GSPL_SH_BWD(DEG, true, false, false) else GSPL_SH_BWD(DEG, false, false, false) break;
     switch (degree) { GSPL_SH_BWD_CASE(0) GSPL_SH_BWD_CASE(1) GSPL_SH_BWD_CASE(2) GSPL_SH_BWD_CASE(3) GSPL_SH_BWD_CASE(4) }
 #undef GSPL_SH_BWD_CASE
 #undef GSPL_SH_BWD
@@ -608,7 +630,7 @@ extern "C" int gspl_sh_bwd(int N, int degree, int n_coeffs,
                            const float* v_colors, int v_colors_stride,
                            float* v_dc, float* v_rest, float* v_dirs, void* stream) {
     return gspl::sh_bwd_launch(N, 1, degree, n_coeffs, dirs, origin, gspl::ShCoeffs{dc, dc_stride, rest, rest_stride}, mask, nullptr, flags, clamped, v_colors,
-                               v_colors_stride > 0 ? v_colors_stride : 3, gspl::ShGrads{v_dc, v_rest}, v_dirs, stream, nullptr, nullptr);
+                               v_colors_stride > 0 ? v_colors_stride : 3, gspl::ShGrads{v_dc, v_rest}, v_dirs, stream, nullptr, nullptr, false);
 }
 
 // Backward of gspl_sh_fwd_batched: v_colors [C,N,3] (dense) -> v_dc / v_rest summed over the cameras, written once.
@@ -618,5 +640,5 @@ extern "C" int gspl_sh_bwd_batched(int C, int N, int degree, int n_coeffs,
                                    const int32_t* radii, int flags, const uint8_t* clamped,
                                    const float* v_colors, float* v_dc, float* v_rest, void* stream) {
     return gspl::sh_bwd_launch(N, C, degree, n_coeffs, means, origins, gspl::ShCoeffs{nullptr, dc_stride, nullptr, rest_stride}, nullptr, radii, flags, clamped,
-                               v_colors, 3, gspl::ShGrads{v_dc, v_rest}, nullptr, stream, nullptr, nullptr);
+                               v_colors, 3, gspl::ShGrads{v_dc, v_rest}, nullptr, stream, nullptr, nullptr, false);
 }

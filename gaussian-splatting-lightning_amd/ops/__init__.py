@@ -66,6 +66,7 @@ class _OpsPackage(_types.ModuleType):
     KEEP_LAST_RASTER = _forward("keep_last_raster")
     SIDE_LOW_PRIORITY = _forward("side_low_priority")
     SEGMENTED_BACKWARD = _forward("segmented_backward")
+    SPARSE_TAIL = _forward("sparse_tail")
     LAST_RASTER = _forward("last_raster")
     SPECULATION = _forward("speculation")
     PENDING_UPDATES = _forward("pending_updates")

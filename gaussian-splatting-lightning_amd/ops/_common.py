@@ -87,6 +87,21 @@ def _attach_hit_mask(target, hit):
         target.has_hit_any_pixels = hit.view(torch.bool)
 
 
+GRAD_ROWS_ATTR = "_gspl_grad_rows"
+
+
+def _attach_grad_rows(flags, *grads):
+    """Hands the sparse backward's row flags (1 = the row may hold a non-zero gradient) to `FusedAdam.step`: (flags, the gradient's
+    `_version` now) as an attribute of each gradient's STORAGE object.  Not of the tensor: autograd hands `.grad` a detached alias, a
+    new Python object, while the storage object travels with the memory and dies with it.  No reference to the gradient tensors is
+    kept anywhere (a second one would make AccumulateGrad clone them), and nothing is keyed on an address (the allocator reuses
+    them).  Whatever writes the gradient afterwards — accumulation, an in-place edit — moves `_version`; a replaced gradient has
+    another storage: `optimizers._grad_rows_of` then finds nothing to use and Adam reads the gradient as always."""
+    for g in grads:
+        if g is not None:
+            setattr(g.untyped_storage(), GRAD_ROWS_ATTR, (flags, g._version))
+
+
 class _side_stream:
     """`with _side_stream(dev) as s:` runs the enclosed launches on a per-device side stream that first waits for everything
     already enqueued on the current stream; `s.join()` makes the current stream wait for them.  Set GSPL_SIDE_STREAM=0 to

@@ -4,7 +4,7 @@ where it matters), so that several devices in one process and the viewer's threa
 internal/viewer/client.py:114) never share a slot that belongs to another device.
 
     STATE.fused_inria, .device_side_list_length, .speculative_emit, .track_hit_pixels, .keep_last_raster, .side_low_priority,
-          .segmented_backward
+          .segmented_backward, .sparse_tail
     STATE.last_isects[(device index, tiles x, tiles y)]    list length of the last frame (introspection)
     STATE.capacity                                          ListCapacity: the room the next frame's speculative emission gets (per device, tile grid)
     STATE.speculation                                       how the guesses fared (frames / cold / misses; bench.py reports them)
@@ -61,7 +61,7 @@ class ListCapacity:
 
 class RuntimeState:
     __slots__ = ("fused_inria", "device_side_list_length", "speculative_emit", "track_hit_pixels", "keep_last_raster", "side_low_priority",
-                 "segmented_backward",
+                 "segmented_backward", "sparse_tail",
                  "last_isects", "capacity", "speculation", "events", "pinned_words", "pinned_ends", "pending_updates", "last_raster", "consts",
                  "identity_slots", "zero_scalars", "new_event", "backward_optimizers", "stats_in_backward", "backward_stats")
 
@@ -88,6 +88,10 @@ class RuntimeState:
         # walks never leaves the plain kernels; "always": every frame (tests); False (=0): never.
         _seg = env("GSPL_SEGMENTED_BWD", "1")
         self.segmented_backward = False if _seg == "0" else ("always" if _seg == "always" else True)
+        # the fused Inria backward of a frame that leaves most splats without a gradient (gspl_rasterize_inria_bwd_sparse): the gradient
+        # arrays are cleared beside the compositing backward, the per-splat kernels behind it write only the rows that have a gradient,
+        # and FusedAdam does not read the gradient of the others.  GSPL_SPARSE_TAIL=0: the dense kernels (the same values).
+        self.sparse_tail: bool = env("GSPL_SPARSE_TAIL", "1") != "0"
         self.last_isects: dict = {}
         self.capacity = ListCapacity()
         self.speculation: dict = {"frames": 0, "cold": 0, "misses": 0}

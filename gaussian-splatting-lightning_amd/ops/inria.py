@@ -11,7 +11,8 @@ from torch import Tensor
 from .. import _lib as L
 from ._state import STATE as S
 from ._frame import FrameBlocks
-from ._common import _packed_row_stride, _guarded, _f32c, _grad_or_zeros, _side_stream, colour_stream, _await_updates, _attach_hit_mask
+from ._common import (_packed_row_stride, _guarded, _f32c, _grad_or_zeros, _side_stream, colour_stream, _await_updates, _attach_hit_mask,
+                      _attach_grad_rows)
 from .binning import MAX_ISECTS, bin_gaussians_begin, bin_gaussians_end
 
 # =============================================================================================
@@ -327,6 +328,8 @@ class _InriaFusedFn(torch.autograd.Function):
             v_sh = None if has_precomp_colors else torch.empty_like(sh)
             v_sh_rest = None if sh_rest is None else torch.empty_like(sh_rest)
             v_cp = E(N, 3) if has_precomp_colors else None
+        # the sparse tail (STATE.sparse_tail): the C side clears the gradient arrays itself and says which rows it then wrote
+        grad_rows = torch.empty((N,), dtype=torch.uint8, device=dev) if (plan is None and S.sparse_tail and N > 0) else None
         if N > 0:
             try:
                 with torch.cuda.device(dev):
@@ -335,6 +338,11 @@ class _InriaFusedFn(torch.autograd.Function):
                                L.ptr(sh_rest), L.ptr(opac), L.ptr(viewm), L.ptr(projm), L.ptr(campos), L.ptr(bg), tanfovx, tanfovy, scale_modifier,
                                L.ptr(radii), ctypes.byref(ctx.state), L.ptr(v_out), L.ptr(packed), L.ptr(hit), L.ptr(scratch), L.ptr(v_ndc),
                                ctypes.byref(plan), L.stream())
+                    elif grad_rows is not None:
+                        L.call("gspl_rasterize_inria_bwd_sparse", degree, n_coeffs, L.ptr(means3D), L.ptr(scales), L.ptr(rotations), L.ptr(sh),
+                               L.ptr(sh_rest), L.ptr(opac), L.ptr(viewm), L.ptr(projm), L.ptr(campos), L.ptr(bg), tanfovx, tanfovy, scale_modifier,
+                               L.ptr(radii), ctypes.byref(ctx.state), L.ptr(v_out), L.ptr(packed), L.ptr(hit), L.ptr(v_means), L.ptr(v_ndc), L.ptr(v_sh),
+                               L.ptr(v_sh_rest), L.ptr(v_cp), L.ptr(v_opac), L.ptr(v_scales), L.ptr(v_quats), L.ptr(v_cov), L.ptr(grad_rows), L.stream())
                     else:
                         L.call("gspl_rasterize_inria_bwd", degree, n_coeffs, L.ptr(means3D), L.ptr(scales), L.ptr(rotations), L.ptr(sh), L.ptr(sh_rest),
                                L.ptr(opac), L.ptr(viewm), L.ptr(projm), L.ptr(campos), L.ptr(bg), tanfovx, tanfovy, scale_modifier, L.ptr(radii),
@@ -352,6 +360,9 @@ class _InriaFusedFn(torch.autograd.Function):
             if S.keep_last_raster and S.last_raster is not None:
                 # introspection (tests): the compositing backward's own per-splat rows, x y | a b c | opacity | r g b
                 S.last_raster["packed_grads"] = packed
+                S.last_raster["grad_rows"] = grad_rows
+            if grad_rows is not None:
+                _attach_grad_rows(grad_rows, v_means, v_sh, v_cp, v_opac, v_scales, v_quats, v_cov, v_sh_rest)
         else:
             for t in (v_means, v_ndc, v_opac):
                 t.zero_()

@@ -22,6 +22,26 @@ from . import _lib as L
 DEFERRED_BLOCKS = int(__import__("os").environ.get("GSPL_ADAM_DEFERRED_BLOCKS", "0"))
 
 
+def _grad_rows_of(items, N):
+    """The row flags of the sparse Inria backward (`ops._common._attach_grad_rows`) if they describe EVERY gradient of one launch as
+    it is now, else None.  Every gradient must be the very memory the backward returned — its storage object carries (flags, version) —
+    unwritten since (`_version` as recorded: accumulation and in-place edits move it), whole (the parameter's shape, from the storage's
+    first byte to its last), and all of them must carry the same flags tensor, one byte per row."""
+    from .ops._common import GRAD_ROWS_ATTR
+    flags = None
+    for (p, g, _m, _v, _lr, _row) in items:
+        storage = g.untyped_storage()
+        tag = getattr(storage, GRAD_ROWS_ATTR, None)
+        if tag is None or tag[1] != g._version or (flags is not None and tag[0] is not flags):
+            return None
+        if g.shape != p.shape or g.storage_offset() != 0 or storage.nbytes() != 4 * g.numel() or not g.is_contiguous():
+            return None
+        flags = tag[0]
+    if flags is None or flags.shape != (N,) or flags.dtype != torch.uint8 or not flags.is_contiguous():
+        return None
+    return flags
+
+
 class _FusedAdamBase(torch.optim.Optimizer):
     _bias_correction = True
 
@@ -148,8 +168,10 @@ class _FusedAdamBase(torch.optim.Optimizer):
         st["step"] = int(st["step"]) + 1
         return st
 
-    def _run(self, batches, visibility: Optional[torch.Tensor], max_blocks: int = 0):
-        """batches: {(device, rows, b1, b2, eps, step): [(param, grad, exp_avg, exp_avg_sq, lr, row_elems), ...]} -> launches."""
+    def _run(self, batches, visibility: Optional[torch.Tensor], max_blocks: int = 0, use_grad_rows: bool = False):
+        """batches: {(device, rows, b1, b2, eps, step): [(param, grad, exp_avg, exp_avg_sq, lr, row_elems), ...]} -> launches.
+        use_grad_rows: gradients the sparse Inria backward left may come with its row flags (`_grad_rows_of`); the update is the same,
+        the kernel then does not read the gradient of rows it knows to be zero."""
         for (dev, N, b1, b2, eps, step), items in batches.items():
             vis = None
             if visibility is not None:
@@ -160,14 +182,21 @@ class _FusedAdamBase(torch.optim.Optimizer):
             bc2s = math.sqrt(1.0 - b2 ** step) if self._bias_correction else 1.0
             for i in range(0, len(items), L.GSPL_ADAM_MAX_TENSORS):
                 chunk = items[i:i + L.GSPL_ADAM_MAX_TENSORS]
+                rows = _grad_rows_of(chunk, N) if use_grad_rows else None
+                if rows is not None and rows.device != dev:
+                    rows = None
                 table = (L.AdamTensor * len(chunk))()
                 for k, (p, g, m, v, lr, row) in enumerate(chunk):
                     if m.shape != p.shape or v.shape != p.shape or not m.is_contiguous() or not v.is_contiguous() or m.dtype != torch.float32:
                         raise RuntimeError("fused Adam: exp_avg / exp_avg_sq must be contiguous fp32 tensors of the parameter's shape")
                     table[k] = L.AdamTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), lr, row)
                 with torch.cuda.device(dev):
-                    L.call("gspl_selective_adam_limited", len(chunk), table, N, L.ptr(vis),
-                           float(b1), float(b2), float(eps), float(bc1), float(bc2s), int(max_blocks), L.stream())
+                    if rows is None:
+                        L.call("gspl_selective_adam_limited", len(chunk), table, N, L.ptr(vis),
+                               float(b1), float(b2), float(eps), float(bc1), float(bc2s), int(max_blocks), L.stream())
+                    else:
+                        L.call("gspl_selective_adam_rows", len(chunk), table, N, L.ptr(vis), L.ptr(rows),
+                               float(b1), float(b2), float(eps), float(bc1), float(bc2s), int(max_blocks), L.stream())
 
     def _launch(self, visibility: Optional[torch.Tensor]):
         L.lib()
@@ -197,7 +226,7 @@ class _FusedAdamBase(torch.optim.Optimizer):
                 key = (p.device, N, b1, b2, group["eps"], st["step"] if self._bias_correction else 0)
                 dst = later if (defer_group or id(p) in self._deferred_ids) else batches
                 dst.setdefault(key, []).append((p, g, st["exp_avg"], st["exp_avg_sq"], float(group["lr"]), row))
-        self._run(batches, visibility)
+        self._run(batches, visibility, use_grad_rows=True)
         if later:
             self._run_deferred(later, visibility)
 

@@ -462,6 +462,22 @@ int gspl_rasterize_inria_bwd(int degree, int n_coeffs,
                              float* packed, uint8_t* hit_flags /*nullable*/,
                              float* v_means3D, float* v_means2D_ndc, float* v_shs, float* v_shs_rest, float* v_colors_precomp, float* v_opacities,
                              float* v_scales, float* v_rotations, float* v_cov3D, void* stream);
+/* The same backward for frames in which most splats get no gradient (additive entry, GSPL_ABI_VERSION stays 39; a saturated scene
+ * blends ~50 splats per pixel and leaves nine rows in ten exactly zero).  The v_* arrays are cleared on the library's low-priority stream
+ * BESIDE the compositing backward (forked from and joined into `stream` with events), and the per-splat kernels behind it then read
+ * the geometry of, and write, only the rows whose packed gradient row is not all zero; the densification statistics of the state are
+ * applied to every visible row as always.  grad_rows [N] u8 (written): 1 = the row may hold a non-zero gradient, 0 = all 59 floats
+ * (and v_means2D_ndc) of the row are zero.  Every output equals gspl_rasterize_inria_bwd's as a value; where that one computes a zero
+ * from a negative factor it writes -0, this one leaves +0. */
+int gspl_rasterize_inria_bwd_sparse(int degree, int n_coeffs,
+                                    const float* means3D, const float* scales, const float* rotations, const float* shs, const float* shs_rest,
+                                    const float* opacities,
+                                    const float* viewmatrix, const float* projmatrix, const float* campos, const float* bg,
+                                    float tanfovx, float tanfovy, float scale_modifier,
+                                    const int32_t* radii, const gspl_inria_state* state, const float* v_out_color,
+                                    float* packed, uint8_t* hit_flags /*nullable*/,
+                                    float* v_means3D, float* v_means2D_ndc, float* v_shs, float* v_shs_rest, float* v_colors_precomp, float* v_opacities,
+                                    float* v_scales, float* v_rotations, float* v_cov3D, uint8_t* grad_rows, void* stream);
 
 /* The backward with the OPTIMIZER INSIDE (additive entry, round 5): the per-Gaussian kernels that end the backward apply the Adam update
  * to the rows they have just produced the gradient of — moments read and written once, parameters written once, NO parameter gradient in
@@ -680,6 +696,14 @@ int gspl_selective_adam(int n_tensors, const gspl_adam_tensor* tensors /* host a
 int gspl_selective_adam_limited(int n_tensors, const gspl_adam_tensor* tensors, int N, const uint8_t* visible /*nullable*/,
                                 float beta1, float beta2, float eps, float bias_correction1, float bias_correction2_sqrt,
                                 int max_blocks, void* stream);
+/* The same update told which rows have a gradient at all (additive entry, GSPL_ABI_VERSION stays 39): grad_rows [N] u8, device,
+ * nullable; 0 = EVERY gradient element of that row, in every tensor of the call, is zero (gspl_rasterize_inria_bwd_sparse leaves such an
+ * array).  All rows are updated as always (Adam moves a row with g = 0); in tensors of 32 or more floats per row a 16-byte chunk whose
+ * rows all carry 0 is updated with a zero from a register instead of its gradient from memory.  Same parameters and moments. */
+int gspl_selective_adam_rows(int n_tensors, const gspl_adam_tensor* tensors, int N, const uint8_t* visible /*nullable*/,
+                             const uint8_t* grad_rows /*nullable*/,
+                             float beta1, float beta2, float eps, float bias_correction1, float bias_correction2_sqrt,
+                             int max_blocks, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * 10. Stable LSD radix sort of the binning stage, exported for the parity tests.
