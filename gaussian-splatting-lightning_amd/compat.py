@@ -13,6 +13,14 @@ op of `gspl_amd.ops` with the same signature.  With them the reference's OWN ren
 published gsplat `utils.py`; parity with the fork's own build of it is unpinned (there is no ROCm build to compare against).
 Functions of the fork that are not built (`compute_relocation`, `rasterize_to_vis_aware_weights`) are left out: importing them
 raises ImportError as it would without the package.
+For the Periodic Vibration Gaussian route (internal/renderers/periodic_vibration_gaussian_renderer.py:9,
+internal/model_components/envlight.py:2) two more stand-ins exist, each with the ONE function that route calls: `nvdiffrast.torch`
+with `texture` — cube maps only (tex [1, 6, R, R, 3], uv [B, H, W, 3], filter_mode='linear', boundary_mode='cube', no mip-maps, no
+gradient for uv), served by `ops.cubemap_sample` with the published OpenGL / nvdiffrast semantics; parity with nvdiffrast's own build
+is unpinned; everything else of nvdiffrast (rasterisation, 2D textures, antialiasing) is NOT built and raises — and `kornia.utils` with
+`create_meshgrid` in plain torch; nothing else of kornia is built.  With them the reference's own PVG renderer and `EnvLight` import
+unedited (the call `EnvLight.forward` makes is tested through the stand-in on the GPU; a whole forward pass of the reference's renderer on
+them is untested); `HipPeriodicVibrationGaussianRenderer` is the route that is tested end to end.
 
 The reference imports them by their own module names inside functions, e.g.
 `from simple_knn._C import distCUDA2` (internal/models/vanilla_gaussian.py:122) or `from fused_ssim import fused_ssim`
@@ -100,6 +108,33 @@ def _depth_to_normal(depths, camtoworlds, Ks, z_depth=True):
     return torch.stack(maps).reshape(*lead, H, W, 3)
 
 
+def _texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode="auto", boundary_mode="wrap", max_mip_level=None):
+    """`nvdiffrast.torch.texture` for the one form the reference uses (envlight.py:20): a cube map tex [1, 6, R, R, 3] sampled along
+    uv [B, H, W, 3] with filter_mode='linear' and boundary_mode='cube' -> [B, H, W, 3].  Anything else raises NotImplementedError."""
+    from . import ops
+    if uv_da is not None or mip_level_bias is not None or mip is not None or max_mip_level is not None:
+        raise NotImplementedError("mip-mapped texture sampling is not built")
+    if filter_mode != "linear" or boundary_mode != "cube":
+        raise NotImplementedError(f"only filter_mode='linear' with boundary_mode='cube' is built, got {filter_mode!r} / {boundary_mode!r}")
+    if tex.dim() != 5 or tex.shape[0] != 1 or tex.shape[1] != 6 or tex.shape[2] != tex.shape[3]:
+        raise NotImplementedError(f"tex must be one cube map [1, 6, R, R, 3], got {tuple(tex.shape)}")
+    if uv.dim() != 4 or uv.shape[-1] != 3:
+        raise NotImplementedError(f"uv must be [B, H, W, 3], got {tuple(uv.shape)}")
+    return ops.cubemap_sample(tex[0], uv, filter_mode=filter_mode, boundary_mode=boundary_mode)
+
+
+def _create_meshgrid(height, width, normalized_coordinates=True, device=None, dtype=None):
+    """kornia's `utils.create_meshgrid` as published: [1, H, W, 2], the last axis (x, y); pixel units 0 .. W-1 / 0 .. H-1, or -1 .. 1
+    with normalized_coordinates."""
+    import torch
+    xs = torch.linspace(0, width - 1, width, device=device, dtype=dtype)
+    ys = torch.linspace(0, height - 1, height, device=device, dtype=dtype)
+    if normalized_coordinates:
+        xs = (xs / (width - 1) - 0.5) * 2
+        ys = (ys / (height - 1) - 0.5) * 2
+    return torch.stack(torch.meshgrid([xs, ys], indexing="ij"), dim=-1).permute(1, 0, 2).unsqueeze(0)
+
+
 def _module(name: str, doc: str, **attrs):
     mod = types.ModuleType(name)
     mod.__doc__ = doc
@@ -170,6 +205,18 @@ def install() -> list:
         from . import ops
         _module("fused_ssim", "gspl_amd stand-in for fused_ssim (HIP; see gspl_amd.ops.fused_ssim)", fused_ssim=ops.fused_ssim)
         installed.append("fused_ssim")
+    if _missing("nvdiffrast"):
+        doc = "gspl_amd stand-in for nvdiffrast.torch: `texture` on cube maps only (HIP; gspl_amd.ops.cubemap_sample)"
+        pkg = _module("nvdiffrast", doc)
+        pkg.__path__ = []
+        pkg.torch = _module("nvdiffrast.torch", doc, texture=_texture)
+        installed.append("nvdiffrast.torch")
+    if _missing("kornia"):
+        doc = "gspl_amd stand-in for kornia.utils: `create_meshgrid` only (plain torch)"
+        pkg = _module("kornia", doc)
+        pkg.__path__ = []
+        pkg.utils = _module("kornia.utils", doc, create_meshgrid=_create_meshgrid)
+        installed.append("kornia.utils")
     if _missing("fused_bilagrid"):
         _module("fused_bilagrid", "gspl_amd stand-in for fused_bilagrid (HIP; gspl_amd.bilagrid)",
                 **{n: _late(n, "bilagrid") for n in ("BilateralGrid", "slice", "total_variation_loss")})

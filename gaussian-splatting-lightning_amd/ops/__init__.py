@@ -20,6 +20,9 @@ reference's renderers call (same names, argument meaning and error behaviour):
   Wide feature maps (internal/renderers/feature_3dgs_renderer.py, gsplat_contrastive_feature_renderer.py: `rasterize_gaussians` with
   32 .. 512 channels over a frozen model)
       rasterize_features
+  Periodic Vibration Gaussians (internal/models/periodic_vibration_gaussian.py, internal/renderers/periodic_vibration_gaussian_renderer.py,
+  internal/model_components/envlight.py: the vibration transform, and `nvdiffrast.torch.texture` on a cube map)
+      pvg_motion, cubemap_sample, envlight_blend
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -50,6 +53,8 @@ from .mcmc import compute_relocation, perturb_means_, mcmc_regularization, mcmc_
 from .bilagrid import bilagrid_slice, bilagrid_tv, _SliceFn, _TvFn
 from .surface import depth_to_normal, gsplat_rays, surfel_maps, surface_reg, _DepthNormalFn, _SurfelMapsFn, _SurfaceRegFn
 from .features import rasterize_features, _FeatureFn
+from .pvg import pvg_motion, _PvgMotionFn
+from .envlight import cubemap_sample, envlight_blend, _CubemapFn, _BlendFn
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

@@ -927,6 +927,61 @@ int gspl_feature_bwd(int N, int64_t n_isects, int D, int mode, int layout,
                      const int32_t* offsets, const int32_t* flatten_ids, const int32_t* last_ids,
                      const float* v_out, float* v_features, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 17. Periodic Vibration Gaussians: the vibration transform (csrc/pvg.hip) and the cube-map sky (csrc/envlight.hip).  PURELY
+ *    ADDITIVE: six new entry points, nothing existing changes, GSPL_ABI_VERSION stays 39.  fp32, device pointers only; what
+ *    internal/models/periodic_vibration_gaussian.py, internal/renderers/periodic_vibration_gaussian_renderer.py and
+ *    internal/model_components/envlight.py compute with some fifteen elementwise launches, a direction grid and nvdiffrast.
+ *
+ *  The vibration transform.  Rows: means, velocity [N,3]; t, scale_t, opacities [N] (scale_t and opacities ACTIVATED, as the model's
+ *  getters return them).  table (DEVICE memory, 6 floats): ts = camera time + time_offset - time_shift | time_shift | 1 when shifted
+ *  else 0 | cycle | velocity_decay | a = 2 pi / cycle.
+ *        avg_velocity = velocity exp(-scale_t / cycle / 2 velocity_decay)
+ *        means_t      = means + velocity sin((ts - t) a) / a,  plus avg_velocity time_shift when shifted
+ *        marginal     = exp(-0.5 (t - ts)^2 / scale_t^2),      opacity_t = opacities marginal
+ *  gspl_pvg_motion_fwd: one launch, every element of means_t, avg_velocity [N,3] and opacity_t [N] written.  N == 0: no launch.
+ *  gspl_pvg_motion_bwd: the three upstream gradients (each nullable = zero) -> g_means, g_velocity [N,3], g_t, g_scale_t,
+ *      g_opacities [N], every element written, in one launch; sin, cos and exp are recomputed from the inputs.  Where marginal
+ *      underflows to 0 (or is undefined) the terms through it are exactly 0: nothing is NaN or infinite there.
+ *
+ *  The cube map.  base [6,R,R,3] (face, row, column, channel), 1 <= R <= 8192; a direction l = (x, y, z):
+ *    - zero or non-finite l: value 0, no gradient.
+ *    - the major axis is x if |x| >= |y| and |x| >= |z|, else y if |y| >= |z|, else z; ma = |major component|; (sc, tc) per face:
+ *        0 (+x): (-z, -y)   1 (-x): (+z, -y)   2 (+y): (+x, +z)   3 (-y): (+x, -z)   4 (+z): (+x, -y)   5 (-z): (-x, -y)
+ *      s = (sc / ma + 1) / 2, t = (tc / ma + 1) / 2; texel coordinates x = s R - 0.5 (column), y = t R - 0.5 (row).
+ *    - bilinear over the four taps around (x, y).  A tap one texel off the face in ONE coordinate is taken from the adjacent face:
+ *      its centre on this face's extended plane is folded over the shared edge (the overflowing coordinate becomes +-1, the former
+ *      major coordinate 1 - 1/R), and the face and nearest texel are selected again from the folded point.  A tap off the face in
+ *      BOTH coordinates is a cube corner and has no texel: it is dropped and the other three weights are divided by their sum.
+ *      R == 1 is legal.
+ *    These are the published OpenGL / nvdiffrast (filter_mode='linear', boundary_mode='cube') semantics; parity with nvdiffrast's own
+ *    build is UNPINNED (it cannot be built here); the fp64 restatement in tests/pvg_oracle.py pins this implementation.
+ *  gspl_cubemap_fwd: dirs [M,3] -> out [M,3], every element written.
+ *  gspl_cubemap_bwd: g_base [6,R,R,3] += weights v_out — ZEROED BY THE CALLER, fp32 atomics (the order of the additions is not
+ *      fixed).  There is no gradient for the directions.
+ *  gspl_envlight_blend_fwd: table (DEVICE, 13 floats): the camera-to-world rotation [3,3] row-major | fx | fy | cx | cy.  Per pixel
+ *      (u, v): d = normalize(((u - cx + ju) / fx, (v - cy + jv) / fy, 1)) with (ju, jv) = jitter[:, v, u] (jitter [2,H,W], nullable
+ *      = 0.5); l = swap(rotation d), swap(x, y, z) = (x, z, -y); out [3,H,W] = rgb + (1 - alpha) sample(l), rgb [3,H,W], alpha
+ *      [H,W].  dirs_out [H,W,3] (nullable) receives l.
+ *  gspl_envlight_blend_bwd: v_out [3,H,W] -> g_alpha [H,W] (nullable) = -sum_c v_out_c sample(l)_c, written; g_base (nullable,
+ *      ZEROED BY THE CALLER) += weights (1 - alpha) v_out, fp32 atomics.  (The gradient of rgb is v_out itself.)  The direction
+ *      and the taps are recomputed.
+ * ---------------------------------------------------------------------------------------- */
+int gspl_pvg_motion_fwd(int N, const float* means, const float* velocity, const float* t, const float* scale_t,
+                        const float* opacities, const float* table, float* means_t, float* avg_velocity, float* opacity_t,
+                        void* stream);
+int gspl_pvg_motion_bwd(int N, const float* velocity, const float* t, const float* scale_t, const float* opacities,
+                        const float* table, const float* v_means_t /*nullable*/, const float* v_avg_velocity /*nullable*/,
+                        const float* v_opacity_t /*nullable*/, float* g_means, float* g_velocity, float* g_t, float* g_scale_t,
+                        float* g_opacities, void* stream);
+int gspl_cubemap_fwd(int64_t M, int R, const float* dirs, const float* base, float* out, void* stream);
+int gspl_cubemap_bwd(int64_t M, int R, const float* dirs, const float* v_out, float* g_base, void* stream);
+int gspl_envlight_blend_fwd(int H, int W, int R, const float* table, const float* rgb, const float* alpha, const float* base,
+                            const float* jitter /*nullable*/, float* out, float* dirs_out /*nullable*/, void* stream);
+int gspl_envlight_blend_bwd(int H, int W, int R, const float* table, const float* alpha, const float* base,
+                            const float* jitter /*nullable*/, const float* v_out, float* g_alpha /*nullable*/,
+                            float* g_base /*nullable*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
