@@ -88,6 +88,86 @@ def write_ply_vertices(path: str, vertices: np.ndarray) -> None:
         f.write(body.tobytes())
 
 
+def write_ply_mesh(path: str, vertices, faces, colors=None) -> None:
+    """A triangle mesh as binary_little_endian PLY: `x y z` float, optionally `red green blue` uchar (round(clip(c, 0, 1) * 255)),
+    and the faces as `vertex_indices`, a uchar-counted list of int."""
+    vertices = np.asarray(vertices, dtype="<f4").reshape(-1, 3)
+    faces = np.asarray(faces).reshape(-1, 3)
+    if faces.size and (faces.min() < 0 or faces.max() >= vertices.shape[0]):
+        raise ValueError(f"{path}: a face refers to a vertex outside [0, {vertices.shape[0]})")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {vertices.shape[0]}", "property float x", "property float y",
+              "property float z"]
+    if colors is not None:
+        colors = np.asarray(colors, dtype=np.float64).reshape(-1, 3)
+        if colors.shape[0] != vertices.shape[0]:
+            raise ValueError(f"{path}: {colors.shape[0]} colours for {vertices.shape[0]} vertices")
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
+    header += [f"element face {faces.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    vertex_rows = np.empty(vertices.shape[0], dtype=fields)
+    for i, name in enumerate("xyz"):
+        vertex_rows[name] = vertices[:, i]
+    if colors is not None:
+        bytes_ = np.rint(np.clip(colors, 0.0, 1.0) * 255.0).astype("u1")
+        for i, name in enumerate(("red", "green", "blue")):
+            vertex_rows[name] = bytes_[:, i]
+    face_rows = np.empty(faces.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    face_rows["n"] = 3
+    face_rows["v"] = faces
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(vertex_rows.tobytes())
+        f.write(face_rows.tobytes())
+
+
+def read_ply_mesh(path: str):
+    """What `write_ply_mesh` writes -> (vertices [N,3] float32, faces [T,3] int32, colors [N,3] uint8 or None).  Triangles only,
+    binary_little_endian only."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        element, counts, props, fmt = None, {}, {"vertex": [], "face": []}, None
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: truncated PLY header")
+            tok = line.decode("ascii", "replace").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                element = tok[1]
+                if element not in props or element in counts or (element == "face" and "vertex" not in counts):
+                    raise ValueError(f"{path}: expected one vertex element followed by one face element, got `{element}`")
+                counts[element] = int(tok[2])
+            elif tok[0] == "property":
+                props[element].append(tok[1:])
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian":
+            raise ValueError(f"{path}: only binary_little_endian meshes are read, got {fmt}")
+        if props["face"] != [["list", "uchar", "int", "vertex_indices"]] or any(p[0] == "list" for p in props["vertex"]):
+            raise ValueError(f"{path}: faces must be one `list uchar int vertex_indices` property")
+        vdt = np.dtype([(name, "<" + _PLY_TYPES[kind]) for kind, name in props["vertex"]])
+        fdt = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+        nv, nf = counts.get("vertex", 0), counts.get("face", 0)
+        raw_v, raw_f = f.read(nv * vdt.itemsize), f.read(nf * fdt.itemsize)
+        if len(raw_v) != nv * vdt.itemsize or len(raw_f) != nf * fdt.itemsize:
+            raise ValueError(f"{path}: truncated mesh data")
+    v, fa = np.frombuffer(raw_v, dtype=vdt, count=nv), np.frombuffer(raw_f, dtype=fdt, count=nf)
+    if nf and not (fa["n"] == 3).all():
+        raise ValueError(f"{path}: only triangles are read")
+    vertices = np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float32) if nv else np.zeros((0, 3), np.float32)
+    colors = np.stack([v["red"], v["green"], v["blue"]], axis=1) if nv and "red" in vdt.names else (
+        np.zeros((0, 3), np.uint8) if "red" in (vdt.names or ()) else None)
+    return vertices, fa["v"].copy(), colors
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Gaussian model <-> PLY / state dict
 # ---------------------------------------------------------------------------------------------------------------------

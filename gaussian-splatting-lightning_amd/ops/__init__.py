@@ -23,6 +23,8 @@ reference's renderers call (same names, argument meaning and error behaviour):
   Periodic Vibration Gaussians (internal/models/periodic_vibration_gaussian.py, internal/renderers/periodic_vibration_gaussian_renderer.py,
   internal/model_components/envlight.py: the vibration transform, and `nvdiffrast.torch.texture` on a cube map)
       pvg_motion, cubemap_sample, envlight_blend
+  2DGS mesh extraction (internal/utils/gs2d_mesh_utils.py: the per-camera TSDF fusion in torch, `skimage.measure.marching_cubes`)
+      tsdf_init, tsdf_table, tsdf_fuse, marching_tetrahedra, marching_tetrahedra_soup, index_soup
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -55,6 +57,7 @@ from .surface import depth_to_normal, gsplat_rays, surfel_maps, surface_reg, _De
 from .features import rasterize_features, _FeatureFn
 from .pvg import pvg_motion, _PvgMotionFn
 from .envlight import cubemap_sample, envlight_blend, _CubemapFn, _BlendFn
+from .mesh import tsdf_init, tsdf_table, tsdf_fuse, marching_tetrahedra, marching_tetrahedra_soup, index_soup
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

@@ -982,6 +982,75 @@ int gspl_envlight_blend_bwd(int H, int W, int R, const float* table, const float
                             const float* jitter /*nullable*/, const float* v_out, float* g_alpha /*nullable*/,
                             float* g_base /*nullable*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 18. Mesh extraction for the 2DGS route (csrc/mesh.hip): TSDF fusion of depth maps and marching tetrahedra.  PURELY ADDITIVE: three
+ *    new entry points and one constant, nothing existing changes, GSPL_ABI_VERSION stays 39.  fp32 data, device pointers only, no
+ *    atomics of any kind; every output is bit-reproducible.  What internal/utils/gs2d_mesh_utils.py (`extract_mesh_unbounded`) computes
+ *    with some twenty launches and four masked scatters per camera and chunk, and a marching cubes on the CPU.
+ *
+ *  gspl_tsdf_fuse: the running average of V views at M samples, one launch, state updated in place.
+ *    The samples.  points [M,3] when not NULL.  points == NULL: a block of a lattice that is never materialised.  The lattice has
+ *      n = (n0, n1, n2) nodes, the block starts at node b = (b0, b1, b2) and has m = (m0, m1, m2) nodes (0 <= b, b + m <= n,
+ *      M == m0 m1 m2); sample index ((i m1) + j) m2 + k, k fastest, is node g = b + (i, j, k), at
+ *          s_a = fmaf((float)g_a, step_a, lo_a),  step_a = (hi_a - lo_a) / (float)(n_a - 1)     for n_a > 1,        s_a = lo_a for n_a == 1:
+ *      the difference and the quotient rounded to fp32, then ONE rounding of lo + g step (in numpy: the float64 sum of lo and the exact
+ *      float64 product, rounded to float32).  Blocks of one lattice therefore see bit-identical nodes on the planes they share, and a
+ *      node is within half an ulp of its own value however much lo cancels.  With points the nine lattice integers are ignored.
+ *    table (DEVICE memory, GSPL_TSDF_TABLE_FLOATS = 16 floats): center[3] | radius | voxel_size | sdf_trunc (<= 0: 5 voxel_size) |
+ *      depth_trunc (<= 0: none) | contract (0 or 1) | with_rgb (0 or 1) | lo[3] | hi[3] | 0.
+ *    view_table [V,16]: each view's full projection, row-major, ROW-VECTOR convention (p = (x, 1) P, as the reference's cameras hold
+ *      `full_projection`); depth [V,H,W]; rgb [V,3,H,W] (nullable).  State: tsdf [M], weight [M], color [M,3] (nullable).  Colour is
+ *      fused when the table's with_rgb is set AND rgb and color are both not NULL; otherwise color is neither read nor written.
+ *    Per sample s:
+ *      contract:  mag = |s|;  T = sdf_trunc, times 1 / (2 - min(mag, 1.9)) where mag > 1;  u = s where mag < 1, else
+ *                 (1 / (2 - mag)) (s / mag);  x = u radius + center.        Without contract: x = s, T = sdf_trunc.
+ *      for v = 0 .. V-1, in this order:
+ *        p = (x, 1) P_v,  z = p.w,  pix = p.xy / p.w;  the view counts if -1 < pix.x, pix.y < 1 and z > 0;
+ *        d = the bilinear sample of depth_v at pix, align_corners=True, border padding: ix = (pix.x + 1) / 2 (W - 1) clamped to
+ *            [0, W-1], x0 = floor(ix), x1 = min(x0 + 1, W - 1), likewise in y (valid for W == 1 or H == 1: the one tap);
+ *        it further needs d - z > -T and, with depth_trunc > 0, 0 < d <= depth_trunc.  (The depth_trunc cut is the bounded mode's; it
+ *            is NOT in the reference's torch path, which Open3D's integration applies to its depth images instead.)
+ *        if it counts:  tsdf = (tsdf w + clamp((d - z) / T, -1, 1)) / (w + 1);  color likewise with the same taps of rgb_v;  w += 1.
+ *      Everything up to and including the clamped quotient (and the colour sample) is evaluated in fp64 from the fp32 inputs and rounded
+ *      to fp32 once; the average is fmaf(tsdf, w, value) / (w + 1) in fp32.  The kernel CONTINUES from the state it is given: the
+ *      caller initialises tsdf = 1, weight = 1, color = 0 as the reference does, and fusing views [0, a) and then [a, V) in two calls
+ *      gives the bits of one call (cameras of several image sizes, or a bounded map stack, are fused stack by stack).
+ *    M == 0 or V == 0: no launch, returns 0, the state is untouched.  One thread per sample, 64-bit indexing throughout
+ *    (V H W and 3 M may pass 2^31).  A NaN or infinite projection fails the pixel test: the view does not count and nothing is read.
+ *
+ *  gspl_mtet_count / gspl_mtet_emit: the iso-surface of volume [X,Y,Z] (k fastest) by marching tetrahedra.  No case table, no
+ *    ambiguous case, and a closed 2-manifold wherever the surface does not leave the volume.
+ *    Decomposition.  Cell (i, j, k), i < X-1, j < Y-1, k < Z-1, with first corner v0 = (i, j, k), is cut into the six Kuhn
+ *      tetrahedra: for the permutations (a, b, c) of the axes (0, 1, 2) in lexicographic order, corners v0, v0 + e_a, v0 + e_a + e_b,
+ *      v0 + e_a + e_b + e_c.  The same under every translation: neighbouring cells agree on the faces they share.
+ *    Inside.  A corner is inside iff value < level (a NaN is outside).
+ *    Cases.  Stable-partition the four corners, inside ones first, and name them 0..3.  One inside corner: the triangle on edges
+ *      (0,1) (0,2) (0,3); three: (0,3) (1,3) (2,3); two: (0,2) (0,3) (1,3) and then (0,2) (1,3) (1,2).  A triangle has its last two
+ *      vertices swapped when its normal points from the centroid of the outside corners towards the centroid of the inside ones;
+ *      the test is exact, in integers, on the edge midpoints of the unit cell (it is the same for every crossing point and every
+ *      positive step).  Normals point from inside to outside: a closed surface around an inside region has positive signed volume.
+ *    Vertices.  A vertex lies on a lattice edge between nodes A and B, A the one with the lower global linear index whichever is
+ *      inside:  t = (level - f_A) / (f_B - f_A),  p_a = fmaf(t, pB_a - pA_a, pA_a),  pN_a = fmaf((float)node_a, step_a, origin_a) with
+ *      the GLOBAL node index: every triangle of every block that uses the edge computes the same bits, and with origin = lo,
+ *      step = (hi - lo) / (n - 1) a node lies where gspl_tsdf_fuse's lattice put it.  grid (DEVICE memory, 6 floats): origin[3] of
+ *      global node 0 | step[3], step > 0.
+ *    Keys.  key = global_linear_index(A) * 8 + direction, int64; the global index is ((g_0 G1) + g_1) G2 + g_2 with g = b + local node
+ *      and the caller's global dimensions G = (g0, g1, g2) and block offset b (0 <= b, b + (X, Y, Z) <= G); direction of B - A:
+ *      (1,0,0) 0, (0,1,0) 1, (0,0,1) 2, (1,1,0) 3, (1,0,1) 4, (0,1,1) 5, (1,1,1) 6.  Blocks that share a plane give equal keys on it.
+ *    gspl_mtet_count: counts [(X-1)(Y-1)(Z-1)] u8, cell-major (k fastest): the cell's triangles, at most 12.
+ *    gspl_mtet_emit: offsets = the EXCLUSIVE prefix sum of counts (int32), total = its end (the one number the host reads) ->
+ *      vertices [3 total, 3] and keys [3 total], triangle after triangle: cell-major, then the tetrahedra in the order above, then the
+ *      triangles in the order above.  A cell whose offset and count do not fit [0, total] writes nothing.
+ *    X, Y or Z < 2, or total == 0: no launch, returns 0.
+ * ---------------------------------------------------------------------------------------- */
+#define GSPL_TSDF_TABLE_FLOATS 16
+int gspl_tsdf_fuse(int64_t M, const float* points /*nullable*/, int n0, int n1, int n2, int b0, int b1, int b2, int m0, int m1, int m2,
+                   const float* table, int V, int H, int W, const float* view_table, const float* depth, const float* rgb /*nullable*/,
+                   float* tsdf, float* weight, float* color /*nullable*/, void* stream);
+int gspl_mtet_count(int X, int Y, int Z, const float* volume, float level, uint8_t* counts, void* stream);
+int gspl_mtet_emit(int X, int Y, int Z, const float* volume, float level, const float* grid, int g0, int g1, int g2,
+                   int b0, int b1, int b2, const int32_t* offsets, int64_t total, float* vertices, int64_t* keys, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
