@@ -44,7 +44,10 @@ static_assert(B2CHUNK <= B2_NT || B2_NW == 2, "a round is staged by one pass of 
 // forward, which decides whether the following frames run segmented).  1: the workgroup walks segment 0 of its tile — the whole walk when it
 // is at most SEG entries — and publishes the other segments of a longer walk as work items.  2: the launch behind it: one workgroup
 // per item slot, the published items are served, the other workgroups leave at once.
-template <int D, int MODE, bool CHW, bool ABS, bool PACKED, int SEGM = 0>
+// FILL (the sparse tail of the fused Inria backward, fused.hip; SEGM 0 or 1): the launch's first fill.blocks workgroups — a multiple of
+// 8, so that the tile -> XCD mapping of the others is the plain launch's — clear the arrays of `fill` and leave before any barrier; the
+// walk of tile xcd_remap(blockIdx.x - fill.blocks) is unchanged.  The arrays are written again only by kernels behind this one.
+template <int D, int MODE, bool CHW, bool ABS, bool PACKED, int SEGM = 0, bool FILL = false>
 __global__ __launch_bounds__(B2_NT, GSPL_BWD2_WAVES) void composite_bwd2_kernel(
     int n_tiles, int tile_w, int width, int height, int64_t n_isects,
     const float* __restrict__ means2d, const float* __restrict__ conics, const float* __restrict__ colors,
@@ -54,10 +57,16 @@ __global__ __launch_bounds__(B2_NT, GSPL_BWD2_WAVES) void composite_bwd2_kernel(
     const float* __restrict__ v_out_colors, const float* __restrict__ v_out_alphas,
     float* __restrict__ v_means2d, float* __restrict__ v_means2d_abs,
     float* __restrict__ v_conics, float* __restrict__ v_colors, float* __restrict__ v_opacities, int packed_stride,
-    uint8_t* __restrict__ hit_flags, SegState seg) {
+    uint8_t* __restrict__ hit_flags, SegState seg, FillJob fill) {
     using TR = ModeTraits<MODE>;
     constexpr int NV = BwdVals<D, ABS>::N;
     constexpr int RS = BwdRec<D>::STRIDE;
+    static_assert(!FILL || SEGM != 2, "the fill rides on the first launch");
+    int block = blockIdx.x;
+    if constexpr (FILL) {
+        if (block < fill.blocks) { zero_fill_body<B2_NT>(fill, (unsigned)block, (unsigned)fill.blocks); return; }
+        block -= fill.blocks;
+    }
     constexpr bool VO_REGS = D <= 4;                  // dL/dout of the lane's phase-2 column lives in registers
     constexpr int SLAB = 2 * P2_SLOTS * 128;          // floats per wave: fac plane, sp plane, [slot][column*8 + row]
     static_assert(NV <= 16, "one ds_add round per batch");
@@ -79,11 +88,11 @@ __global__ __launch_bounds__(B2_NT, GSPL_BWD2_WAVES) void composite_bwd2_kernel(
     // leaves at once.  A loop over items instead keeps every kernel argument alive across the walk: 106 scalar registers, spills.)
     int tile = 0, segidx = 0;
     if constexpr (SEGM == 2) {
-        if (blockIdx.x >= min(*seg.count(), seg.slots)) return;
-        const uint32_t item = seg.work()[blockIdx.x];
+        if ((uint32_t)block >= min(*seg.count(), seg.slots)) return;
+        const uint32_t item = seg.work()[block];
         tile = (int)(item >> 8); segidx = (int)(item & 255u);
     } else {
-        tile = xcd_remap(blockIdx.x, n_tiles);
+        tile = xcd_remap(block, n_tiles);
     }
     {
     const int tx = (tile % tile_w) * TILE, ty = (tile / tile_w) * TILE;
@@ -549,28 +558,44 @@ static int launch_bwd(bool absgrad, int n_tiles, int tile_w, ImageSize image, co
                       const float* final_Ts, const int32_t* last_ids,
                       const float* v_out_colors, const float* v_out_alphas,
                       float* v_means2d, float* v_means2d_abs, float* v_conics, float* v_colors, float* v_opacities,
-                      hipStream_t s, int packed_stride, uint8_t* hit_flags, ListTiles lt, const SegState* seg_in = nullptr) {
+                      hipStream_t s, int packed_stride, uint8_t* hit_flags, ListTiles lt, const SegState* seg_in = nullptr, const FillJob* fill = nullptr) {
 #define GSPL_BWD_ARGS n_tiles, tile_w, image.width, image.height, lists.n_isects, sp.means2d, sp.conics, sp.colors, sp.opacities, sp.backgrounds, \
                       lists.offsets, lists.flatten_ids, final_Ts, last_ids, v_out_colors, v_out_alphas, v_means2d, v_means2d_abs, v_conics, v_colors, v_opacities,   \
                       packed_stride, hit_flags
+    const FillJob no_fill{};
     if (lt.log2 != 4) {       // lists on 8- or 32-pixel tiles: the block-wise compatibility kernel
+        if (fill) return fail_arg("composite_bwd: the fill rides on the 16-pixel kernel only");
         if (absgrad) hipLaunchKernelGGL((composite_bwd_block_kernel<D, MODE, CHW, true, PACKED>), dim3(4 * n_tiles), dim3(64), 0, s, GSPL_BWD_ARGS, lt);
         else hipLaunchKernelGGL((composite_bwd_block_kernel<D, MODE, CHW, false, PACKED>), dim3(4 * n_tiles), dim3(64), 0, s, GSPL_BWD_ARGS, lt);
         return check_launch("composite_bwd");
     }
     SegState plain = {};
     if (seg_in) { plain.host_flag = seg_in->host_flag; plain.walk = seg_in->walk; }
+    // the first regular-gradient launch, SEGM 0 or 1: it carries the fused Inria call's fill
+    constexpr bool CAN_FILL = (D == 3 || D == 4) && MODE == GSPL_MODE_INRIA && CHW && PACKED;
+    if (fill && (!CAN_FILL || absgrad || fill->blocks <= 0 || (fill->blocks & 7)))
+        return fail_arg("composite_bwd: the fill rides on the Inria mode's CHW packed kernel (3 or 4 channels, no absgrad) with a multiple of 8 workgroups");
+    auto first_launch = [&](auto segm, const SegState& sg) {
+        if constexpr (CAN_FILL) {
+            if (fill) {
+                hipLaunchKernelGGL((composite_bwd2_kernel<D, MODE, CHW, false, PACKED, decltype(segm)::value, true>), dim3(n_tiles + fill->blocks), dim3(B2_NT), 0, s,
+                                   GSPL_BWD_ARGS, sg, *fill);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((composite_bwd2_kernel<D, MODE, CHW, false, PACKED, decltype(segm)::value>), dim3(n_tiles), dim3(B2_NT), 0, s, GSPL_BWD_ARGS, sg, no_fill);
+    };
     if constexpr ((D == 3 || (D == 4 && MODE == GSPL_MODE_INRIA)) && CHW && PACKED) {
         // the segmented form (the fused Inria call with checkpoints from its forward): regular gradients only — the deterministic mode
         // and absgrad keep the one-workgroup-per-tile walk
         if (seg_in && seg_in->ckpt && (D == 3 || seg_in->ckpt_x) && !absgrad && packed_stride > 0) {
-            hipLaunchKernelGGL((composite_bwd2_kernel<D, MODE, CHW, false, PACKED, 1>), dim3(n_tiles), dim3(B2_NT), 0, s, GSPL_BWD_ARGS, *seg_in);
-            hipLaunchKernelGGL((composite_bwd2_kernel<D, MODE, CHW, false, PACKED, 2>), dim3(seg_in->slots), dim3(B2_NT), 0, s, GSPL_BWD_ARGS, *seg_in);
+            first_launch(std::integral_constant<int, 1>{}, *seg_in);
+            hipLaunchKernelGGL((composite_bwd2_kernel<D, MODE, CHW, false, PACKED, 2>), dim3(seg_in->slots), dim3(B2_NT), 0, s, GSPL_BWD_ARGS, *seg_in, no_fill);
             return check_launch("composite_bwd(segmented)");
         }
     }
-    if (absgrad) hipLaunchKernelGGL((composite_bwd2_kernel<D, MODE, CHW, true, PACKED>), dim3(n_tiles), dim3(B2_NT), 0, s, GSPL_BWD_ARGS, plain);
-    else hipLaunchKernelGGL((composite_bwd2_kernel<D, MODE, CHW, false, PACKED>), dim3(n_tiles), dim3(B2_NT), 0, s, GSPL_BWD_ARGS, plain);
+    if (absgrad) hipLaunchKernelGGL((composite_bwd2_kernel<D, MODE, CHW, true, PACKED>), dim3(n_tiles), dim3(B2_NT), 0, s, GSPL_BWD_ARGS, plain, no_fill);
+    else first_launch(std::integral_constant<int, 0>{}, plain);
 #undef GSPL_BWD_ARGS
     return check_launch("composite_bwd");
 }
@@ -695,13 +720,14 @@ extern "C" int gspl_composite_bwd_packed(int N, int64_t n_isects, int D, int mod
 
 int gspl::composite_bwd_packed_impl(int N, int D, int mode, int layout, const CompositeSplats& sp, ImageSize image, TileGrid grid, const TileLists& lists,
                                     const float* final_Ts, const int32_t* last_ids, const float* v_out_colors, const float* v_out_alphas,
-                                    float* v_packed, int packed_stride, int absgrad, uint8_t* hit_flags, void* stream, const SegState* seg) {
+                                    float* v_packed, int packed_stride, int absgrad, uint8_t* hit_flags, void* stream, const SegState* seg,
+                                    const FillJob* fill) {
     using namespace gspl;
     const int64_t n_isects = lists.n_isects;
     int rc = check_composite_args(N, n_isects, D, mode, layout, image, grid, "composite_bwd_packed: bad argument");
     if (rc != GSPL_OK) return rc;
     if (packed_stride < 6 + D + (absgrad ? 2 : 0)) return fail_arg("composite_bwd_packed: packed_stride smaller than the row");
-    if (n_isects == 0 || N == 0) return GSPL_OK;
+    if (n_isects == 0 || N == 0) return fill ? fail_arg("composite_bwd_packed: a fill needs a launch to ride on") : GSPL_OK;
     if (!sp.means2d || !sp.conics || !sp.colors || !sp.opacities || !lists.offsets || !lists.flatten_ids || !final_Ts || !last_ids || !v_out_colors || !v_packed)
         return fail_arg("composite_bwd_packed: NULL required pointer");
     const ListTiles lt = list_tiles(grid);
@@ -726,7 +752,7 @@ int gspl::composite_bwd_packed_impl(int N, int D, int mode, int layout, const Co
     rc = dispatch_composite(D, mode, layout, [&](auto d, auto m, auto chw) {
         return launch_bwd<d(), m(), chw(), true>(ag, n_tiles, ctw, image, sp, lists,
                                                  final_Ts, last_ids, v_out_colors, v_out_alphas, v_packed, nullptr, nullptr, nullptr, nullptr, s, packed_stride,
-                                                 hit_flags, lt, seg);
+                                                 hit_flags, lt, seg, fill);
     });
     if (ordered) {
         if (rc == GSPL_OK) rc = ordered_reduce(N, n_isects, nv, lists.flatten_ids, entries, v_packed_out, packed_stride_out, s, "composite_bwd_packed(ordered reduce)");

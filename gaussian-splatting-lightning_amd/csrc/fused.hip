@@ -166,13 +166,12 @@ static unsigned long long next_ticket() {
 #ifndef GSPL_EVENT_FLAGS
 #define GSPL_EVENT_FLAGS hipEventDisableTiming
 #endif
-struct FrameEvents { hipEvent_t geo = nullptr, col = nullptr, cnt = nullptr, fork = nullptr, filled = nullptr; bool ok = false; };
+struct FrameEvents { hipEvent_t geo = nullptr, col = nullptr, cnt = nullptr; bool ok = false; };
 static FrameEvents& frame_events() {
     static thread_local FrameEvents ev;
     if (!ev.ok)
         ev.ok = hipEventCreateWithFlags(&ev.geo, GSPL_EVENT_FLAGS) == hipSuccess && hipEventCreateWithFlags(&ev.col, GSPL_EVENT_FLAGS) == hipSuccess &&
-                hipEventCreateWithFlags(&ev.cnt, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&ev.fork, GSPL_EVENT_FLAGS) == hipSuccess && hipEventCreateWithFlags(&ev.filled, GSPL_EVENT_FLAGS) == hipSuccess;
+                hipEventCreateWithFlags(&ev.cnt, hipEventDisableTiming) == hipSuccess;
     return ev;
 }
 
@@ -462,68 +461,30 @@ extern "C" int gspl_rasterize_inria_fwd(
 }
 
 namespace gspl {
-// The sparse tail of the backward (gspl_rasterize_inria_bwd_sparse): the gradient arrays are cleared BESIDE the compositing backward —
-// a VALU-bound kernel that leaves HBM at 5 % — on the library's low-priority stream, and the two per-splat kernels behind it then write
-// only the rows that have a gradient.  One bounded grid over a table of the arrays, streaming stores: the compositing kernel keeps its
-// wave slots and its L2.  How many workgroups: the fill has the ~300 us of the compositing backward to write 236 MB (1 M splats), and
-// the faster it writes the more it delays that kernel's loads — measured at 1 M splats, 1080p (profiles/sparse_tail_fill_grid.txt):
-// 256 workgroups fill in 52 us and stretch composite_bwd2 by 9 us, 64 in 83 us and by 2.5 us, 24 in 148 us and by nothing.
+// The sparse tail of the backward (gspl_rasterize_inria_bwd_sparse): the gradient arrays are cleared INSIDE the compositing backward's
+// launch — a VALU-bound kernel that leaves HBM at 5 % — by a few extra workgroups at the front of its grid (composite_bwd.hip, FILL),
+// and the per-splat kernels behind it then write only the rows that have a gradient.  Stream order is the only dependency: no second
+// stream, no event in front of the compositing kernel or behind it.  One bounded grid over a table of the arrays, streaming stores: the
+// compositing kernel keeps its wave slots and its L2.  How many workgroups (of 128 threads, the compositing kernel's): the fill has the
+// ~300 us of the compositing backward to write 236 MB (1 M splats), and the faster it writes the more it delays that kernel's loads
+// (profiles/tail_fill_in_grid.txt).  A frame without lists has no compositing launch: the fill is then a launch of its own.
 #ifndef GSPL_FILL_BLOCKS
 #define GSPL_FILL_BLOCKS 32
 #endif
-static int fill_blocks() {      // (GSPL_FILL_BLOCKS in the environment: A/B runs of what the fill costs the kernel it runs beside)
-    static const int n = [] { const char* e = getenv("GSPL_FILL_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 && v <= 65536 ? v : GSPL_FILL_BLOCKS; }();
+static int fill_blocks() {      // (GSPL_FILL_BLOCKS in the environment: A/B runs of what the fill costs the kernel it rides in; rounded up to a multiple of 8)
+    static const int n = [] { const char* e = getenv("GSPL_FILL_BLOCKS"); const int v = e ? atoi(e) : 0; return ((v > 0 && v <= 65536 ? v : GSPL_FILL_BLOCKS) + 7) & ~7; }();
     return n;
 }
-struct FillJob {
-    struct Span { float* p; uint64_t n; } a[9];      // n: floats
-    int count = 0;
-    void add(float* p, uint64_t n) { if (p && n) a[count++] = Span{p, n}; }
-};
-__global__ __launch_bounds__(256) void zero_fill_kernel(FillJob job) {
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    const uint64_t tid = (uint64_t)blockIdx.x * 256 + threadIdx.x, stride = (uint64_t)gridDim.x * 256;
-    for (int k = 0; k < job.count; ++k) {
-        float* p = job.a[k].p;
-        const uint64_t n = job.a[k].n;
-        // floats in front of the first 16-byte boundary, 16-byte chunks, floats behind the last one
-        const uint64_t head = min(n, (uint64_t)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2));
-        const uint64_t n4 = (n - head) >> 2, tail0 = head + (n4 << 2);
-        v4f* q = reinterpret_cast<v4f*>(p + head);
-        const v4f z = {0.f, 0.f, 0.f, 0.f};
-        for (uint64_t i = tid; i < n4; i += stride) __builtin_nontemporal_store(z, q + i);
-        if (tid < head) p[tid] = 0.f;
-        if (tid < n - tail0) p[tail0 + tid] = 0.f;
-    }
-}
-// Joins the fill into the caller's stream: explicitly in front of the first kernel that writes the arrays, and on every other way out
-// (the caller frees the arrays in its stream's order).
-struct FillJoin {
-    hipStream_t s; hipEvent_t ev = nullptr;
-    explicit FillJoin(hipStream_t st) : s(st) {}
-    FillJoin(const FillJoin&) = delete;
-    void join() { if (ev) (void)hipStreamWaitEvent(s, ev, 0); ev = nullptr; }
-    ~FillJoin() { join(); }
-};
-static int zero_grads_beside(int N, const InriaParams& p, const InriaGrads& v, hipStream_t s, FillJoin& fill) {
+__global__ __launch_bounds__(256) void zero_fill_kernel(FillJob job) { zero_fill_body<256>(job, blockIdx.x, gridDim.x); }
+static FillJob grads_fill_job(int N, const InriaParams& p, const InriaGrads& v) {
     FillJob job;
     const uint64_t n = (uint64_t)N, sh_rows = (uint64_t)(p.n_coeffs > 0 ? p.n_coeffs : 0);
     job.add(v.means, 3 * n); job.add(v.means2d_ndc, 3 * n); job.add(v.opacities, n);
     job.add(v.scales, 3 * n); job.add(v.quats, 4 * n); job.add(v.cov3d_precomp, 6 * n); job.add(v.colors_precomp, 3 * n);
     if (v.shs_rest) { job.add(v.shs, 3 * n); job.add(v.shs_rest, 3 * (sh_rows > 0 ? sh_rows - 1 : 0) * n); }
     else job.add(v.shs, 3 * sh_rows * n);
-    FrameEvents& fe = frame_events();
-    if (!fe.ok) return check_hip(hipGetLastError(), "rasterize_inria_bwd: event");
-    hipStream_t ls = (hipStream_t)gspl_low_priority_stream();
-    const bool side = ls && ls != s;
-    if (side) {      // the arrays are the caller's fresh allocations: what its stream did with that memory before has to be over
-        (void)hipEventRecord(fe.fork, s);
-        (void)hipStreamWaitEvent(ls, fe.fork, 0);
-    }
-    hipLaunchKernelGGL(zero_fill_kernel, dim3(fill_blocks()), dim3(256), 0, side ? ls : s, job);
-    const int rc = check_launch("rasterize_inria_bwd: clear the gradients");
-    if (side) { (void)hipEventRecord(fe.filled, ls); fill.ev = fe.filled; }
-    return rc;
+    job.blocks = fill_blocks();
+    return job;
 }
 
 // cam: width and height come from the state; p.cov3d: the forward's
@@ -542,12 +503,8 @@ static int rasterize_inria_bwd_impl(InriaParams p, const float* opacities, Inria
     const bool aa = (st->flags & GSPL_INRIA_ANTIALIAS) != 0, invd = (st->flags & GSPL_INRIA_INVDEPTH) != 0;
     const int D = invd ? 4 : 3, prow = invd ? 10 : 9;
     const float* caller_opacities = opacities;      // (aa: the backward of the compensation reads them, raw or activated)
-    FillJoin fill(s);
-    if (grad_rows) {
-        if (plan) return fail_arg("rasterize_inria_bwd: grad_rows and the optimizer inside the backward exclude each other");
-        const int rc = zero_grads_beside(N, p, v, s, fill);
-        if (rc != GSPL_OK) return rc;
-    }
+    if (grad_rows && plan) return fail_arg("rasterize_inria_bwd: grad_rows and the optimizer inside the backward exclude each other");
+    const FillJob fill = grad_rows ? grads_fill_job(N, p, v) : FillJob{};      // the sparse tail: the gradient arrays are cleared on the way
     if (!(st->flags & GSPL_INRIA_PACKED_READY)) {      // (else `packed` is the forward's GSPL_BUF_PACKED block, cleared by its compositing kernel)
         e = hipMemsetAsync(packed, 0, (size_t)N * prow * sizeof(float), s);      // x y | a b c | opacity | r g b (| 1/z)
         if (e != hipSuccess) return check_hip(e, "rasterize_inria_bwd: clear");
@@ -577,10 +534,13 @@ static int rasterize_inria_bwd_impl(InriaParams p, const float* opacities, Inria
         const int rc = composite_bwd_packed_impl(N, D, GSPL_MODE_INRIA, GSPL_LAYOUT_CHW, CompositeSplats{st->means2d, st->conics, st->colors, opacities, bg},
                                                  ImageSize{cam.width, cam.height}, tile_grid16(cam.width, cam.height),
                                                  TileLists{st->offsets, st->flatten_ids, st->n_isects}, st->final_Ts, st->last_ids, v_out_color, nullptr,
-                                                 packed, prow, 0, hit_flags, s, &seg);
+                                                 packed, prow, 0, hit_flags, s, &seg, grad_rows ? &fill : nullptr);
+        if (rc != GSPL_OK) return rc;
+    } else if (grad_rows) {      // no lists, no compositing launch to ride in
+        hipLaunchKernelGGL(zero_fill_kernel, dim3(fill.blocks), dim3(256), 0, s, fill);
+        const int rc = check_launch("rasterize_inria_bwd: clear the gradients");
         if (rc != GSPL_OK) return rc;
     }
-    fill.join();
     return inria_preprocess_bwd_impl(N, p, cam, radii, st->clamped, SplatGradRows::packed(packed, prow), v, st->sh_jac,
                                      aa ? caller_opacities : (raw ? st->opacities : nullptr), s, plan, BwdStats{st->stats_accum, st->stats_denom, st->stats_max_radii},
                                      st->flags & (GSPL_INRIA_RAW_PARAMS | GSPL_INRIA_ANTIALIAS | GSPL_INRIA_INVDEPTH), grad_rows);
@@ -602,7 +562,7 @@ extern "C" int gspl_rasterize_inria_bwd(
                                     InriaGrads{v_means3D, v_scales, v_rotations, v_cov3D, v_shs, v_shs_rest, v_colors_precomp, v_means2D_ndc, v_opacities}, stream, nullptr);
 }
 
-// The same backward for a saturated frame, in which most splats get no gradient: the gradient arrays are cleared beside the compositing
+// The same backward for a saturated frame, in which most splats get no gradient: the gradient arrays are cleared inside the compositing
 // backward and the per-splat kernels write only the rows that have one; grad_rows [N] says which.  Same values as
 // gspl_rasterize_inria_bwd (a zero may differ in sign).
 extern "C" int gspl_rasterize_inria_bwd_sparse(

@@ -205,6 +205,33 @@ __device__ __forceinline__ void block_list_range(const ListTiles& lt, int bx, in
     end = (t + 1 < lt.n || n_isects < 0) ? offsets[t + 1] : (int)n_isects;
 }
 
+// A table of float arrays to clear, and the grid that clears it: `blocks` workgroups of NT threads each, workgroup `block` of them.
+// Streaming stores (the arrays are read again only by the kernels behind the one that clears them); per array the floats in front of
+// the first 16-byte boundary, 16-byte chunks, the floats behind the last one.  Runs as a launch of its own (zero_fill_kernel, fused.hip)
+// or as the role of the first `blocks` workgroups of composite_bwd2_kernel<.., FILL = true>.
+struct FillJob {
+    struct Span { float* p; uint64_t n; } a[9];      // n: floats
+    int count = 0;
+    int blocks = 0;
+    void add(float* p, uint64_t n) { if (p && n) a[count++] = Span{p, n}; }
+};
+template <int NT>
+__device__ __forceinline__ void zero_fill_body(const FillJob& job, unsigned block, unsigned blocks) {
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    const uint64_t tid = (uint64_t)block * NT + threadIdx.x, stride = (uint64_t)blocks * NT;
+    for (int k = 0; k < job.count; ++k) {
+        float* p = job.a[k].p;
+        const uint64_t n = job.a[k].n;
+        const uint64_t head = min(n, (uint64_t)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2));
+        const uint64_t n4 = (n - head) >> 2, tail0 = head + (n4 << 2);
+        v4f* q = reinterpret_cast<v4f*>(p + head);
+        const v4f z = {0.f, 0.f, 0.f, 0.f};
+        for (uint64_t i = tid; i < n4; i += stride) __builtin_nontemporal_store(z, q + i);
+        if (tid < head) p[tid] = 0.f;
+        if (tid < n - tail0) p[tail0 + tid] = 0.f;
+    }
+}
+
 // number of per-splat gradient values accumulated per (tile, splat): xy(2) conic(3) opacity(1) colour(D) [+abs xy(2)]
 template <int D, bool ABS> struct BwdVals { static constexpr int N = 6 + D + (ABS ? 2 : 0); };
 
@@ -219,9 +246,12 @@ int check_composite_args(int N, int64_t n_isects, int D, int mode, int layout, I
 // gspl_composite_fwd / gspl_composite_bwd_packed with the segmentation state of the fused Inria call (fused.hip); seg == NULL: off
 int composite_fwd_impl(int N, int D, int mode, int layout, const CompositeSplats& splats, ImageSize image, TileGrid grid, const TileLists& lists,
                        float* out_colors, float* out_alphas, float* final_Ts, int32_t* last_ids, uint8_t* hit_flags, void* stream, const SegState* seg);
+// `fill` (fused.hip, the sparse tail of the Inria backward; NULL everywhere else): arrays to clear, by fill->blocks extra workgroups at
+// the FRONT of the first composite_bwd2_kernel launch.  Needs the Inria mode, CHW, D 3 or 4, 16-pixel list tiles, no absgrad.
 int composite_bwd_packed_impl(int N, int D, int mode, int layout, const CompositeSplats& splats, ImageSize image, TileGrid grid, const TileLists& lists,
                               const float* final_Ts, const int32_t* last_ids, const float* v_out_colors, const float* v_out_alphas,
-                              float* v_packed, int packed_stride, int absgrad, uint8_t* hit_flags, void* stream, const SegState* seg);
+                              float* v_packed, int packed_stride, int absgrad, uint8_t* hit_flags, void* stream, const SegState* seg,
+                              const FillJob* fill = nullptr);
 
 // One launch of a kernel family templated on <D, MODE, CHW>: f(D, MODE, CHW) gets the three as std::integral_constants and returns the
 // call's code.  check_composite_args has refused every other mode and layout; a D outside {1, 2, 3, 4, 8} is GSPL_ERR_UNSUPPORTED.

@@ -453,4 +453,54 @@ __device__ __forceinline__ int xcd_remap(int b, int n, int run = GSPL_XCD_RUN) {
     return ((i / run) * 8 + x) * run + (i % run);
 }
 
+// Spherical harmonics (sh.hip; the backward tail of inria.hip evaluates the same basis)
+// basis values b[0..K) for unit direction (x,y,z)
+__device__ __forceinline__ void sh_basis(int degree, float x, float y, float z, float* b) {
+    b[0] = 0.28209479177387814f;
+    if (degree < 1) return;
+    b[1] = -0.4886025119029199f * y;
+    b[2] = 0.4886025119029199f * z;
+    b[3] = -0.4886025119029199f * x;
+    if (degree < 2) return;
+    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+    b[4] = 1.0925484305920792f * xy;
+    b[5] = -1.0925484305920792f * yz;
+    b[6] = 0.31539156525252005f * (2.f * zz - xx - yy);
+    b[7] = -1.0925484305920792f * xz;
+    b[8] = 0.5462742152960396f * (xx - yy);
+    if (degree < 3) return;
+    b[9] = -0.5900435899266435f * y * (3.f * xx - yy);
+    b[10] = 2.890611442640554f * xy * z;
+    b[11] = -0.4570457994644658f * y * (4.f * zz - xx - yy);
+    b[12] = 0.3731763325901154f * z * (2.f * zz - 3.f * xx - 3.f * yy);
+    b[13] = -0.4570457994644658f * x * (4.f * zz - xx - yy);
+    b[14] = 1.445305721320277f * z * (xx - yy);
+    b[15] = -0.5900435899266435f * x * (xx - 3.f * yy);
+    if (degree < 4) return;
+    b[16] = 2.5033429417967046f * xy * (xx - yy);
+    b[17] = -1.7701307697799304f * yz * (3.f * xx - yy);
+    b[18] = 0.9461746957575601f * xy * (7.f * zz - 1.f);
+    b[19] = -0.6690465435572892f * yz * (7.f * zz - 3.f);
+    b[20] = 0.10578554691520431f * (zz * (35.f * zz - 30.f) + 3.f);
+    b[21] = -0.6690465435572892f * xz * (7.f * zz - 3.f);
+    b[22] = 0.47308734787878004f * (xx - yy) * (7.f * zz - 1.f);
+    b[23] = -1.7701307697799304f * xz * (xx - 3.f * yy);
+    b[24] = 0.6258357354491761f * (xx * (xx - 3.f * yy) - yy * (3.f * xx - yy));
+}
+
+// dL/d(mean) through the view direction d = v / |v| from the forward's Jacobian jac[c][xyz] = d colour_c / d d (sh_fwd_kernel) and the
+// clamp-masked colour gradient vc: v_v = (g - d (d.g)) / |v|, g = sum_c vc[c] jac[c].  One copy, so that sh_bwd_kernel and the
+// one-launch tail of inria.hip evaluate the same expression tree.
+__device__ __forceinline__ void sh_dir_grad_jac(const float* vc, const float* __restrict__ jac, float dx, float dy, float dz, float inv, float* g) {
+    float gx = 0.f, gy = 0.f, gz = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        gx += vc[c] * jac[c * 3 + 0];
+        gy += vc[c] * jac[c * 3 + 1];
+        gz += vc[c] * jac[c * 3 + 2];
+    }
+    const float dot = gx * dx + gy * dy + gz * dz;
+    g[0] = (gx - dx * dot) * inv; g[1] = (gy - dy * dot) * inv; g[2] = (gz - dz * dot) * inv;
+}
+
 }  // namespace gspl

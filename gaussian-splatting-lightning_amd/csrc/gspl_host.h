@@ -96,6 +96,23 @@ inline ShCoeffs sh_coeffs(const float* shs, const float* shs_rest, int n_coeffs)
     return shs_rest ? ShCoeffs{shs, 3, shs_rest, stride - 3} : ShCoeffs{shs, stride, shs + 3, stride};
 }
 inline ShGrads sh_grads(float* v_shs, float* v_shs_rest) { return v_shs_rest ? ShGrads{v_shs, v_shs_rest} : ShGrads{v_shs, v_shs + 3}; }
+// How the SH backward kernels (sh.hip, and the one-launch tail of inria.hip) stage a splat's coefficient-gradient row in LDS:
+//   merged  : tile rows are the full [K,3] rows starting at dc (row stride rs = dc_stride), dc at col 0, rest at col 3
+//   separate: tile rows are the `rest` rows (row stride rs = rest_stride); dc is written per lane
+struct ShTile {
+    int rs;       // global row stride (floats)
+    int ls;       // LDS row stride (odd)
+    int merged;   // 1: dc inside the tile at col 0, rest at col 3
+};
+// The layout is decided on the OUTPUT arrays (they have the strides of the inputs); false: the row stride is too small for n_coeffs.
+inline bool sh_grad_tile(const ShGrads& out, int dc_stride, int rest_stride, int n_coeffs, ShTile& tile) {
+    tile.merged = (n_coeffs > 1 && out.rest == out.dc + 3 && dc_stride == rest_stride) ? 1 : 0;
+    tile.rs = tile.merged ? dc_stride : rest_stride;
+    if (n_coeffs > 1 && tile.rs < 3 * (n_coeffs - 1) + (tile.merged ? 3 : 0)) return false;
+    if (n_coeffs <= 1) tile.rs = 1;
+    tile.ls = tile.rs | 1;
+    return true;
+}
 
 // the Inria rasterizer's camera ...
 struct InriaCamera {

@@ -271,7 +271,21 @@ __device__ __forceinline__ void pre_adam_pass(const AdamTarget& T, int64_t base,
 // gradient have been handed to its first threads, in row order: one wave in four then walks the long chain of dependent loads, not all
 // four with a few lanes each.  grad_rows[g] = 1 for the rows that were written, 0 for the others: the optimizer's licence not to read
 // their gradient (adam.hip).  The SH backward's rows are among the 1s: its colour gradient is three columns of the same packed row.
-template <bool ACCUM, bool RAW, bool ADAM = false, bool AA = false, bool INVD = false, bool PREZEROED = false>
+//
+// SHDEG >= 0 (with PREZEROED, ACCUM, neither AA nor INVD; `sh` says where): the ONE per-splat kernel of the sparse tail.  A row that was
+// handed on also runs the SH backward of sh_bwd_kernel<SHDEG, true, false, true> with the forward's direction Jacobian — the same
+// expressions in the same order: the basis, the clamp-masked colour gradient, the direction gradient through sh_jac — before the
+// geometry; v_means is written once, direction gradient + geometry (the sum the ACCUM form makes through memory), and the coefficient
+// rows go out through LDS, TAIL_SH_ROWS of a wave's rows at a time, each row by one wave with 64 consecutive floats per store.
+struct TailSh {
+    const uint8_t* clamped; const float* jac; const float* campos;
+    float* v_dc; float* v_rest;      // as sh_bwd_launch lays them out: rest = dc + 3 when one array holds both
+    int dc_stride, rs, ls, merged, n_coeffs;
+};
+static constexpr int TAIL_SH_ROWS = 16;
+// a value as a store and a load would leave it: no multiply in front of the barrier is contracted into an add behind it
+__device__ __forceinline__ float as_stored(float x) { asm volatile("" : "+v"(x)); return x; }
+template <bool ACCUM, bool RAW, bool ADAM = false, bool AA = false, bool INVD = false, bool PREZEROED = false, int SHDEG = -1>
 __global__ __launch_bounds__(256) void inria_preprocess_bwd_kernel(
     int N,
     const float* means, const float* scales, const float* quats,
@@ -283,12 +297,15 @@ __global__ __launch_bounds__(256) void inria_preprocess_bwd_kernel(
     float* __restrict__ v_means, float* __restrict__ v_scales, float* __restrict__ v_quats,
     float* __restrict__ v_cov3d_precomp, float* __restrict__ v_means2d_ndc,
     const float* __restrict__ v_opac_src, float* __restrict__ v_opac_dst, const float* __restrict__ opac_act, PreAdam adam, BwdStats stats,
-    uint8_t* __restrict__ grad_rows) {
+    uint8_t* __restrict__ grad_rows, TailSh sh) {
+    constexpr bool TAIL = SHDEG >= 0;
+    static_assert(!TAIL || (PREZEROED && ACCUM && !AA && !INVD), "the one-launch tail is the plain sparse frame's");
     // ADAM: the block's 256 rows of gradients meet in LDS and the update runs as FLAT, coalesced 16-byte passes over the block's
     // slice of every array (pre_adam_pass) — a lane-per-row update reads and writes 33 strided dwords per Gaussian three times over
     // (95 us at 1 M, 527 us at 6 M: 3 TB/s); every thread of the block stays for the barrier, rows past N carry nothing.
     __shared__ __attribute__((aligned(16))) float s_grad[ADAM ? 256 * 11 : 4];      // means 768 | scales 768 | quats 1024 | opacities 256
     int g = blockIdx.x * blockDim.x + threadIdx.x;
+    bool tail_row = true;      // PREZEROED: this thread was handed a row with a gradient
     if (!ADAM && !PREZEROED && g >= N) return;
     static_assert(!(ADAM && (AA || INVD)), "the optimizer inside the backward takes neither anti-aliasing nor inverse depth");
     static_assert(!(ADAM && PREZEROED), "the optimizer inside the backward writes no gradient rows");
@@ -323,8 +340,91 @@ __global__ __launch_bounds__(256) void inria_preprocess_bwd_kernel(
         for (int k = 0; k < 4; ++k) { before += k < wave ? s_wave[k] : 0; total += s_wave[k]; }
         if (nz) s_rows[before + __popcll(mine & ((1ull << lane) - 1ull))] = g;
         __syncthreads();
-        if ((int)threadIdx.x >= total) return;
-        g = s_rows[threadIdx.x];
+        // (TAIL: a wave that got a row stays whole — its lanes without one help to store the coefficient rows)
+        if ((int)(TAIL ? (threadIdx.x & ~63u) : threadIdx.x) >= total) return;
+        tail_row = (int)threadIdx.x < total;
+        if (tail_row) g = s_rows[threadIdx.x];
+    }
+    float vdir[3] = {0.f, 0.f, 0.f};      // TAIL: dL/d(mean) through the view direction
+    float pre_p[3] = {0.f, 0.f, 0.f}, pre_S6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, pre_s[3] = {0.f, 0.f, 0.f}, pre_q[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (TAIL) {
+        extern __shared__ __attribute__((aligned(16))) float tail_lds[];      // [4 waves][TAIL_SH_ROWS][sh.ls]
+        constexpr int K = (SHDEG + 1) * (SHDEG + 1);
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const bool has_tile = sh.n_coeffs > 1;
+        // asked for together with what the SH part reads: the geometry part's inputs (every row here has a gradient: it needs them all)
+        if (tail_row) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { pre_p[k] = means[g * 3 + k]; pre_s[k] = scales[g * 3 + k]; }
+#pragma unroll
+            for (int k = 0; k < 6; ++k) pre_S6[k] = cov3d[g * 6 + k];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) pre_q[k] = quats[g * 4 + k];
+        }
+        float vc[3] = {0.f, 0.f, 0.f};
+        float dx = 0.f, dy = 0.f, dz = 1.f, inv = 1.f;
+        float b[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) b[k] = 0.f;
+        bool live = tail_row && radii[g] > 0;
+        if (live) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                vc[c] = v_means2d[(int64_t)g * gs2 + 6 + c];
+                if (sh.clamped[(int64_t)g * 3 + c]) vc[c] = 0.f;
+            }
+            live = vc[0] != 0.f || vc[1] != 0.f || vc[2] != 0.f;
+        }
+        if (live) {
+            dx = pre_p[0]; dy = pre_p[1]; dz = pre_p[2];
+            dx -= sh.campos[0]; dy -= sh.campos[1]; dz -= sh.campos[2];
+            inv = rsqrtf(dx * dx + dy * dy + dz * dz);
+            dx *= inv; dy *= inv; dz *= inv;
+            sh_basis(SHDEG, dx, dy, dz, b);
+            if (SHDEG > 0) sh_dir_grad_jac(vc, sh.jac + (int64_t)g * 9, dx, dy, dz, inv, vdir);
+            float d0[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) d0[c] = b[0] * vc[c];
+            if (!sh.merged || !has_tile) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) sh.v_dc[(int64_t)g * sh.dc_stride + c] = d0[c];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) vdir[j] = as_stored(vdir[j]);
+        if (has_tile) {
+            // a row whose clamp-masked colour gradient is zero writes no coefficient row.  TAIL_SH_ROWS lanes stage their rows, then the
+            // wave stores them one by one; the lanes of a wave that left above are not in the ballots
+            float* wl = tail_lds + wave * (TAIL_SH_ROWS * sh.ls);
+            float* base = sh.merged ? sh.v_dc : sh.v_rest;
+            const int col0 = sh.merged ? 3 : 0;
+            for (int l0 = 0; l0 < 64; l0 += TAIL_SH_ROWS) {
+                const bool mine = live && lane >= l0 && lane < l0 + TAIL_SH_ROWS;
+                unsigned long long todo = __ballot(mine);
+                if (!todo) continue;
+                if (mine) {
+                    float* row = wl + (lane - l0) * sh.ls;
+#pragma unroll
+                    for (int k = 1; k < K; ++k) {
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) row[col0 + (k - 1) * 3 + c] = b[k] * vc[c];
+                    }
+                    for (int j = col0 + (K - 1) * 3; j < sh.rs; ++j) row[j] = 0.f;      // above the active degree
+                    if (sh.merged) { row[0] = b[0] * vc[0]; row[1] = b[0] * vc[1]; row[2] = b[0] * vc[2]; }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                while (todo) {
+                    const int src = __builtin_ctzll(todo);
+                    todo &= todo - 1;
+                    const int64_t dst = (int64_t)__shfl(g, src) * sh.rs;
+                    for (int c = lane; c < sh.rs; c += 64) base[dst + c] = wl[(src - l0) * sh.ls + c];
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+        if (!tail_row) return;
     }
     const bool row = g < N;
     float aa_g = 0.f, aa_o = 0.f, aa_comp = 1.f;
@@ -341,10 +441,10 @@ __global__ __launch_bounds__(256) void inria_preprocess_bwd_kernel(
     if (row && radii[g] > 0) {
         InriaCam cam;
         load_inria_cam(viewmatrix, projmatrix, cam);
-        const float p[3] = {means[g * 3 + 0], means[g * 3 + 1], means[g * 3 + 2]};
+        const float p[3] = {TAIL ? pre_p[0] : means[g * 3 + 0], TAIL ? pre_p[1] : means[g * 3 + 1], TAIL ? pre_p[2] : means[g * 3 + 2]};
         float S6[6];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) S6[k] = cov3d[g * 6 + k];
+        for (int k = 0; k < 6; ++k) S6[k] = TAIL ? pre_S6[k] : cov3d[g * 6 + k];
         InriaGeom G;
         inria_geom(cam, p, S6, width, height, tanfovx, tanfovy, G);
 
@@ -385,8 +485,11 @@ __global__ __launch_bounds__(256) void inria_preprocess_bwd_kernel(
         for (int r = 0; r < 3; ++r) vp[r] += cam.V[r * 4 + 0] * vpv[0] + cam.V[r * 4 + 1] * vpv[1] + cam.V[r * 4 + 2] * vpv[2];
 
         if (ADAM || v_scales) {
-            float s[3] = {scales[g * 3 + 0], scales[g * 3 + 1], scales[g * 3 + 2]};
-            float q[4] = {quats[g * 4 + 0], quats[g * 4 + 1], quats[g * 4 + 2], quats[g * 4 + 3]};
+            float s[3], q[4];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) s[j] = TAIL ? pre_s[j] : scales[g * 3 + j];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) q[j] = TAIL ? pre_q[j] : quats[g * 4 + j];
             float act_s[3] = {1.f, 1.f, 1.f}, inv_norm = 1.f;
             if constexpr (RAW) {
 #pragma unroll
@@ -435,7 +538,8 @@ __global__ __launch_bounds__(256) void inria_preprocess_bwd_kernel(
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        if (ACCUM) v_means[g * 3 + j] += vp[j];
+        if (TAIL) v_means[g * 3 + j] = vdir[j] + vp[j];      // (what ACCUM reads back is the direction gradient)
+        else if (ACCUM) v_means[g * 3 + j] += vp[j];
         else v_means[g * 3 + j] = vp[j];
     }
     if (v_scales) {
@@ -584,7 +688,26 @@ int inria_preprocess_bwd_impl(int N, const InriaParams& p, const InriaCamera& ca
     // [N, grad_stride] buffer (gspl_composite_bwd_packed) and share its row stride
     const int gs2 = grad_stride > 0 ? grad_stride : 2, gs3 = grad_stride > 0 ? grad_stride : 3;
     bool accum = false;
-    if (v_shs) {
+    // The one-launch tail: the plain sparse frame (scales + rotations, SH colours of degree <= 3, the forward's direction Jacobian).
+    // Anti-aliasing, inverse depth, precomputed covariances or colours, degree 4 and a backward without sh_jac stay on the two
+    // PREZEROED kernels below: their branches would cost the common form registers, and none of them is a training default.
+    const bool one_launch = grad_rows && v_shs && sh_jac && v_scales && !v_cov3d_precomp && !v_colors_precomp && degree <= 3 &&
+                            !(ext & (GSPL_INRIA_ANTIALIAS | GSPL_INRIA_INVDEPTH));
+    TailSh tail = {};
+    if (v_shs && one_launch) {
+        if (!shs || !cam.campos || !clamped) return fail_arg("inria_preprocess_bwd: shs/campos/clamped missing");
+        if (degree < 0 || n_coeffs < (degree + 1) * (degree + 1)) return fail_arg("inria_preprocess_bwd: bad degree / n_coeffs");
+        if ((shs_rest == nullptr) != (v_shs_rest == nullptr)) return fail_arg("inria_preprocess_bwd: shs_rest and v_shs_rest go together");
+        const ShCoeffs in = sh_coeffs(shs, shs_rest, n_coeffs);
+        const ShGrads out = sh_grads(v_shs, v_shs_rest);
+        ShTile tile;      // the layout rule of sh_bwd_launch
+        if (!sh_grad_tile(out, in.dc_stride, in.rest_stride, n_coeffs, tile)) return fail_arg("inria_preprocess_bwd: SH row stride too small");
+        // (`clamped` is applied as sh_bwd_launch applies it with GSPL_SH_ADD_HALF_CLAMP, the flag this backward always passes)
+        tail.clamped = clamped; tail.jac = sh_jac; tail.campos = cam.campos;
+        tail.v_dc = out.dc; tail.v_rest = out.rest; tail.dc_stride = in.dc_stride; tail.n_coeffs = n_coeffs;
+        tail.merged = tile.merged; tail.rs = tile.rs; tail.ls = tile.ls;
+        accum = true;
+    } else if (v_shs) {
         if (!shs || !cam.campos || !clamped) return fail_arg("inria_preprocess_bwd: shs/campos/clamped missing");
         if (degree < 0 || degree > 4 || n_coeffs < (degree + 1) * (degree + 1)) return fail_arg("inria_preprocess_bwd: bad degree / n_coeffs");
         // dL/d(dir) lands in v_means; the geometry kernel accumulates on top
@@ -615,13 +738,32 @@ int inria_preprocess_bwd_impl(int N, const InriaParams& p, const InriaCamera& ca
         pre.quats = target(v_quats, plan->rotations);
         pre.opac = target(v_opacities, plan->opacities);
     }
+    if (one_launch) {
+        const size_t lds_bytes = (size_t)4 * TAIL_SH_ROWS * tail.ls * sizeof(float);
+        if (lds_bytes > 64 * 1024) return fail_arg("inria_preprocess_bwd: coefficient row too long for LDS staging");
+        auto launch = [&](auto R, auto DEG) {
+            hipLaunchKernelGGL((inria_preprocess_bwd_kernel<true, R(), false, false, false, true, DEG()>), dim3(grid), dim3(256), lds_bytes, s,
+                               N, means, scales, quats, cov3d, cam.viewmatrix, cam.projmatrix, width, height, cam.tanfovx, cam.tanfovy, cam.scale_modifier,
+                               radii, v_means2d, v_conics, gs2, gs3, v_means, v_scales, v_quats, v_cov3d_precomp, v_means2d_ndc, v_opacities_packed,
+                               v_opacities, opac_act, pre, stats, grad_rows, tail);
+        };
+        dispatch_bools([&](auto R) {
+            switch (degree) {
+                case 0: launch(R, std::integral_constant<int, 0>{}); break;
+                case 1: launch(R, std::integral_constant<int, 1>{}); break;
+                case 2: launch(R, std::integral_constant<int, 2>{}); break;
+                default: launch(R, std::integral_constant<int, 3>{}); break;
+            }
+        }, raw);
+        return check_launch("inria_preprocess_bwd(one-launch tail)");
+    }
     // ADAM goes with neither AA nor INVD nor grad_rows (refused above) and always accumulates (it needs v_shs): the other combinations do not exist
     dispatch_bools([&](auto A, auto R, auto AD, auto AAF, auto INVDF, auto PZ) {
         if constexpr (!AD() || (A() && !AAF() && !INVDF() && !PZ()))
             hipLaunchKernelGGL((inria_preprocess_bwd_kernel<A(), R(), AD(), AAF(), INVDF(), PZ()>), dim3(grid), dim3(256), 0, s,
                                N, means, scales, quats, cov3d, cam.viewmatrix, cam.projmatrix, width, height, cam.tanfovx, cam.tanfovy, cam.scale_modifier,
                                radii, v_means2d, v_conics, gs2, gs3, v_means, v_scales, v_quats, v_cov3d_precomp, v_means2d_ndc, v_opacities_packed,
-                               v_opacities, opac_act, pre, stats, grad_rows);
+                               v_opacities, opac_act, pre, stats, grad_rows, TailSh{});
     }, accum, raw, plan != nullptr, aa, invd, grad_rows != nullptr);
     return check_launch("inria_preprocess_bwd");
 }

@@ -37,39 +37,7 @@ static constexpr int SH_MAX_K = 25;
 __device__ __constant__ const float kC0 = 0.28209479177387814f;
 __device__ __constant__ const float kC1 = 0.4886025119029199f;
 
-// basis values b[0..K) for unit direction (x,y,z)
-__device__ __forceinline__ void sh_basis(int degree, float x, float y, float z, float* b) {
-    b[0] = 0.28209479177387814f;
-    if (degree < 1) return;
-    b[1] = -0.4886025119029199f * y;
-    b[2] = 0.4886025119029199f * z;
-    b[3] = -0.4886025119029199f * x;
-    if (degree < 2) return;
-    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-    b[4] = 1.0925484305920792f * xy;
-    b[5] = -1.0925484305920792f * yz;
-    b[6] = 0.31539156525252005f * (2.f * zz - xx - yy);
-    b[7] = -1.0925484305920792f * xz;
-    b[8] = 0.5462742152960396f * (xx - yy);
-    if (degree < 3) return;
-    b[9] = -0.5900435899266435f * y * (3.f * xx - yy);
-    b[10] = 2.890611442640554f * xy * z;
-    b[11] = -0.4570457994644658f * y * (4.f * zz - xx - yy);
-    b[12] = 0.3731763325901154f * z * (2.f * zz - 3.f * xx - 3.f * yy);
-    b[13] = -0.4570457994644658f * x * (4.f * zz - xx - yy);
-    b[14] = 1.445305721320277f * z * (xx - yy);
-    b[15] = -0.5900435899266435f * x * (xx - 3.f * yy);
-    if (degree < 4) return;
-    b[16] = 2.5033429417967046f * xy * (xx - yy);
-    b[17] = -1.7701307697799304f * yz * (3.f * xx - yy);
-    b[18] = 0.9461746957575601f * xy * (7.f * zz - 1.f);
-    b[19] = -0.6690465435572892f * yz * (7.f * zz - 3.f);
-    b[20] = 0.10578554691520431f * (zz * (35.f * zz - 30.f) + 3.f);
-    b[21] = -0.6690465435572892f * xz * (7.f * zz - 3.f);
-    b[22] = 0.47308734787878004f * (xx - yy) * (7.f * zz - 1.f);
-    b[23] = -1.7701307697799304f * xz * (xx - 3.f * yy);
-    b[24] = 0.6258357354491761f * (xx * (xx - 3.f * yy) - yy * (3.f * xx - yy));
-}
+// (sh_basis: the basis values b[0..K) for a unit direction — gspl_device.h, shared with the one-launch backward tail of inria.hip)
 
 // gradient of sum_k w[k]*b[k] w.r.t. (x,y,z) treated as independent variables
 __device__ __forceinline__ void sh_basis_grad(int degree, float x, float y, float z, const float* w,
@@ -240,14 +208,7 @@ __device__ __forceinline__ void tile_adam(const AdamTarget& T, int64_t base, int
 // `dc` = the separate DC parameter ([N, 1, 3]; unused when merged)
 struct ShAdam { AdamTarget tile, dc; };
 
-// tile geometry:
-//   merged  : tile rows are the full [K,3] rows starting at dc (row stride rs = dc_stride), dc at col 0
-//   separate: tile rows are the `rest` rows (row stride rs = rest_stride); dc is read per lane
-struct ShTile {
-    int rs;       // global row stride (floats)
-    int ls;       // LDS row stride (odd)
-    int merged;   // 1: dc inside the tile at col 0, rest at col 3
-};
+// (ShTile, the tile geometry: gspl_host.h)
 
 // C cameras per launch (C > 1: the Gaussian-sharded renderer evaluates its shard for every rank's camera,
 // gsplat_distributed_renderer.py:252-311): the coefficient rows are staged ONCE and evaluated against C origins; origin,
@@ -383,15 +344,7 @@ __global__ __launch_bounds__(SH_BLOCK) void sh_bwd_kernel(
         if (r < rows) {
             float g[3] = {0.f, 0.f, 0.f};
             if (live && degree > 0) {
-                float gx = 0.f, gy = 0.f, gz = 0.f;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    gx += vc[c] * jac[(int64_t)n * 9 + c * 3 + 0];
-                    gy += vc[c] * jac[(int64_t)n * 9 + c * 3 + 1];
-                    gz += vc[c] * jac[(int64_t)n * 9 + c * 3 + 2];
-                }
-                const float dot = gx * dx + gy * dy + gz * dz;
-                g[0] = (gx - dx * dot) * inv; g[1] = (gy - dy * dot) * inv; g[2] = (gz - dz * dot) * inv;
+                sh_dir_grad_jac(vc, jac + (int64_t)n * 9, dx, dy, dz, inv, g);
             }
             if (!PREZEROED || live) { v_dirs[n * 3 + 0] = g[0]; v_dirs[n * 3 + 1] = g[1]; v_dirs[n * 3 + 2] = g[2]; }
         }
@@ -575,12 +528,7 @@ int sh_bwd_launch(int N, int C, int degree, int n_coeffs, const float* dirs, con
     if (!dirs || !v_colors || !v_dc || (n_coeffs > 1 && !v_rest)) return fail_arg("sh_bwd: NULL required pointer");
     if (v_dirs && !jac && (!dc || (degree > 0 && !rest))) return fail_arg("sh_bwd: v_dirs needs the coefficients (or the forward's Jacobian)");
     ShTile tile;
-    // geometry is decided on the OUTPUT arrays (they have the same strides as the inputs)
-    tile.merged = (n_coeffs > 1 && v_rest == v_dc + 3 && dc_stride == rest_stride) ? 1 : 0;
-    tile.rs = tile.merged ? dc_stride : rest_stride;
-    if (n_coeffs > 1 && tile.rs < 3 * (n_coeffs - 1) + (tile.merged ? 3 : 0)) return fail_arg("sh_bwd: row stride too small");
-    if (n_coeffs <= 1) tile.rs = 1;
-    tile.ls = tile.rs | 1;
+    if (!sh_grad_tile(v_sh, dc_stride, rest_stride, n_coeffs, tile)) return fail_arg("sh_bwd: row stride too small");
     if (v_dirs && !jac && degree > 0) {
         const int in_merged = (rest == dc + 3) ? 1 : 0;
         if (in_merged != tile.merged) return fail_arg("sh_bwd: input/output coefficient layouts differ");
