@@ -21,6 +21,12 @@ is unpinned; everything else of nvdiffrast (rasterisation, 2D textures, antialia
 `create_meshgrid` in plain torch; nothing else of kornia is built.  With them the reference's own PVG renderer and `EnvLight` import
 unedited (the call `EnvLight.forward` makes is tested through the stand-in on the GPU; a whole forward pass of the reference's renderer on
 them is untested); `HipPeriodicVibrationGaussianRenderer` is the route that is tested end to end.
+For the SegAnyGS route (internal/segany_splatting.py:14,273) and the appearance-similarity regulariser
+(internal/metrics/appearance_feature_similarity_regularization_metrics.py:8,70-74) `pytorch3d.ops` exists with the ONE function they
+call, `knn_points`, bound late to `ops.knn_points`: 3-D clouds, K <= 32, no `lengths`, the published semantics with neighbours
+ordered by (d^2, index); parity with pytorch3d's own build is unpinned (there is none for ROCm here).  Nothing else of pytorch3d is
+built: `pytorch3d.ops.iou_box3d` (the partition-LoD renderer's) and everything else keep raising ImportError.  With it
+`SegAnySplatting` imports unedited; `gspl_amd.segany.use_hip_smoothing` then replaces its per-step gather by the fused op.
 
 The reference imports them by their own module names inside functions, e.g.
 `from simple_knn._C import distCUDA2` (internal/models/vanilla_gaussian.py:122) or `from fused_ssim import fused_ssim`
@@ -217,6 +223,12 @@ def install() -> list:
         pkg.__path__ = []
         pkg.utils = _module("kornia.utils", doc, create_meshgrid=_create_meshgrid)
         installed.append("kornia.utils")
+    if _missing("pytorch3d"):
+        doc = "gspl_amd stand-in for pytorch3d.ops: `knn_points` only (HIP; gspl_amd.ops.knn_points)"
+        pkg = _module("pytorch3d", doc)
+        pkg.__path__ = []
+        pkg.ops = _module("pytorch3d.ops", doc, knn_points=_late("knn_points"))
+        installed.append("pytorch3d.ops")
     if _missing("fused_bilagrid"):
         _module("fused_bilagrid", "gspl_amd stand-in for fused_bilagrid (HIP; gspl_amd.bilagrid)",
                 **{n: _late(n, "bilagrid") for n in ("BilateralGrid", "slice", "total_variation_loss")})

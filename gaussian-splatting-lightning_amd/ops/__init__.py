@@ -25,6 +25,9 @@ reference's renderers call (same names, argument meaning and error behaviour):
       pvg_motion, cubemap_sample, envlight_blend
   2DGS mesh extraction (internal/utils/gs2d_mesh_utils.py: the per-camera TSDF fusion in torch, `skimage.measure.marching_cubes`)
       tsdf_init, tsdf_table, tsdf_fuse, marching_tetrahedra, marching_tetrahedra_soup, index_soup
+  SegAnyGS smoothing and the similarity regulariser's search (internal/segany_splatting.py:262-309, `pytorch3d.ops.knn_points`;
+  internal/metrics/appearance_feature_similarity_regularization_metrics.py:70-74; the module-level API is gspl_amd.segany)
+      knn_points, knn_graph, KnnGraph, smooth_features
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -58,6 +61,7 @@ from .features import rasterize_features, _FeatureFn
 from .pvg import pvg_motion, _PvgMotionFn
 from .envlight import cubemap_sample, envlight_blend, _CubemapFn, _BlendFn
 from .mesh import tsdf_init, tsdf_table, tsdf_fuse, marching_tetrahedra, marching_tetrahedra_soup, index_soup
+from .knn import knn_points, knn_graph, KnnGraph, smooth_features, _SmoothFn
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

@@ -1051,6 +1051,45 @@ int gspl_mtet_count(int X, int Y, int Z, const float* volume, float level, uint8
 int gspl_mtet_emit(int X, int Y, int Z, const float* volume, float level, const float* grid, int g0, int g1, int g2,
                    int b0, int b1, int b2, const int32_t* offsets, int64_t total, float* vertices, int64_t* keys, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 19. K nearest neighbours and local feature smoothing for the SegAnyGS route (csrc/knn.hip, csrc/smooth.hip).  PURELY ADDITIVE: six
+ *    new entry points, nothing existing changes (section 7 keeps its results), GSPL_ABI_VERSION stays 39.  fp32 data, device
+ *    pointers only.  What `pytorch3d.ops.knn_points` and the gather / mean of internal/segany_splatting.py:262-309 compute (the latter
+ *    through an [N, S, D] tensor), and what internal/metrics/appearance_feature_similarity_regularization_metrics.py:70-74 queries.
+ *
+ *  gspl_knn_points: for each of the P1 queries p1 [P1,3] the K (1 <= K <= 32) nearest of the P2 reference points p2 [P2,3], exact.
+ *    dists [P1,K] f32: squared Euclidean distances as the kernel's fp32 arithmetic gives them, ascending; idx [P1,K] i64 into p2.
+ *    Order: by (d^2, index) — among equal fp32 d^2 the lower index first; the output is the same bits on every run.  A query that
+ *    coincides with a reference point finds it at distance 0 (p1 == p2: every point is its own first neighbour).  Queries may lie
+ *    anywhere, also far outside the reference cloud.  A reference point with a non-finite coordinate is never returned; where fewer
+ *    than K finite reference points exist the trailing entries of both rows are 0.  A query with a non-finite coordinate gets a row
+ *    of zeros (the call terminates; pytorch3d leaves such a row unspecified).  workspace: gspl_knn_points_workspace_bytes(P2).
+ *    P1 == 0: no launch.  P2 == 0: rows of zeros.
+ *
+ *  gspl_knn_graph: the inverse adjacency of a neighbour map idx [N,K] i32 (values 0 .. N-1; anything else is ignored) in CSR form:
+ *    entries [N K] u32 holds, for row j at [row_start[j], row_start[j+1]), the positions e = i K + k with idx[i,k] == j, ascending
+ *    (i.e. sorted by (i, k)); row_start [N+1] u32.  Built with a count, the exclusive scan and the stable radix sort of section 10:
+ *    deterministic.  The tail of `entries` behind row_start[N] is unspecified.  N K < 2^30.
+ *
+ *  gspl_smooth_features_fwd / _bwd: features [N,D] (1 <= D <= 128), idx [N,K] i32 with values 0 .. N-1 (NOT checked: the caller
+ *    validates the map once, when it builds the graph), mask: bit k set = column k of idx takes part (not 0, no bit >= K), S = its
+ *    population count.
+ *      n_j = x_j / max(|x_j|, 1e-12);   m_i = (1 / S) sum over the selected k of n_idx[i,k];   out_i = m_i / (|m_i| + 1e-9)
+ *    fwd writes out [N,D] and mnorm [N] = |m_i| (the backward needs it), one launch.  bwd: v_features [N,D] = dL/dfeatures from
+ *    v_out [N,D], one launch over the inverse adjacency of the same idx, no atomics, the same bits on every run; it follows torch's
+ *    subgradients at the two guards (|m| == 0: no gradient through |m|; |x| < 1e-12: v_x = v_n / 1e-12).
+ * ---------------------------------------------------------------------------------------- */
+size_t gspl_knn_points_workspace_bytes(int P2);
+int gspl_knn_points(int P1, const float* p1, int P2, const float* p2, int K, float* dists, int64_t* idx,
+                    void* workspace, size_t workspace_bytes, void* stream);
+size_t gspl_knn_graph_workspace_bytes(int N, int K);
+int gspl_knn_graph(int N, int K, const int32_t* idx, uint32_t* row_start, uint32_t* entries,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int gspl_smooth_features_fwd(int N, int D, int K, uint32_t mask, const float* features, const int32_t* idx, float* out, float* mnorm,
+                             void* stream);
+int gspl_smooth_features_bwd(int N, int D, int K, uint32_t mask, const float* features, const uint32_t* row_start, const uint32_t* entries,
+                             const float* out, const float* mnorm, const float* v_out, float* v_features, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
