@@ -27,6 +27,15 @@ call, `knn_points`, bound late to `ops.knn_points`: 3-D clouds, K <= 32, no `len
 ordered by (d^2, index); parity with pytorch3d's own build is unpinned (there is none for ROCm here).  Nothing else of pytorch3d is
 built: `pytorch3d.ops.iou_box3d` (the partition-LoD renderer's) and everything else keep raising ImportError.  With it
 `SegAnySplatting` imports unedited; `gspl_amd.segany.use_hip_smoothing` then replaces its per-step gather by the fused op.
+For the SWAG route (internal/models/swag_model.py:72-78) `tinycudann` exists with ONE class, `Encoding(n_input_dims, encoding_config,
+seed=1337, dtype=None)` (`gspl_amd.hashgrid.Encoding`), for the grid encodings only: otype `HashGrid`, `DenseGrid`, or `Grid` with type
+`Hash` / `Dense`; 2 or 3 input dimensions, 1, 2, 4 or 8 features per level, up to 32 levels, linear interpolation, a float32 table
+(`.params`, uniform in [-1e-4, 1e-4] from the seed) and float32 output, served by `ops.hashgrid_encode` with the published rules of
+tiny-cuda-nn's grid; parity with its own build is unpinned (there is none for ROCm).  Any other otype (Frequency, SphericalHarmonics,
+Identity, ...) or option (Smoothstep, half precision, Tiled) raises NotImplementedError naming it.  `Network`,
+`NetworkWithInputEncoding` and the fused MLPs are NOT built and absent, so `from tinycudann import Network` keeps raising ImportError:
+the reference's renderers that need them (`NetworkFactory(tcnn=True)`) stay unserved, while SWAG's `NetworkFactory(tcnn=False)` MLP is
+plain torch.nn.  With it the reference's own `SWAGModel` / `SWAGRenderer` construct unedited; `HipSWAGRenderer` is the tested route.
 
 The reference imports them by their own module names inside functions, e.g.
 `from simple_knn._C import distCUDA2` (internal/models/vanilla_gaussian.py:122) or `from fused_ssim import fused_ssim`
@@ -229,6 +238,11 @@ def install() -> list:
         pkg.__path__ = []
         pkg.ops = _module("pytorch3d.ops", doc, knn_points=_late("knn_points"))
         installed.append("pytorch3d.ops")
+    if _missing("tinycudann"):
+        from . import hashgrid
+        _module("tinycudann", "gspl_amd stand-in for tinycudann: `Encoding` with a HashGrid / DenseGrid only (HIP; gspl_amd.ops.hashgrid_encode)",
+                Encoding=hashgrid.Encoding)
+        installed.append("tinycudann")
     if _missing("fused_bilagrid"):
         _module("fused_bilagrid", "gspl_amd stand-in for fused_bilagrid (HIP; gspl_amd.bilagrid)",
                 **{n: _late(n, "bilagrid") for n in ("BilateralGrid", "slice", "total_variation_loss")})

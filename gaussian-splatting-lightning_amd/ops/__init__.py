@@ -28,6 +28,8 @@ reference's renderers call (same names, argument meaning and error behaviour):
   SegAnyGS smoothing and the similarity regulariser's search (internal/segany_splatting.py:262-309, `pytorch3d.ops.knn_points`;
   internal/metrics/appearance_feature_similarity_regularization_metrics.py:70-74; the module-level API is gspl_amd.segany)
       knn_points, knn_graph, KnnGraph, smooth_features
+  SWAG's grid encoding (internal/models/swag_model.py:75-78, `tinycudann.Encoding` with otype HashGrid / DenseGrid)
+      hashgrid_levels, HashGridLevels, hashgrid_table, hashgrid_encode, hashgrid_forward, hashgrid_backward
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -62,6 +64,7 @@ from .pvg import pvg_motion, _PvgMotionFn
 from .envlight import cubemap_sample, envlight_blend, _CubemapFn, _BlendFn
 from .mesh import tsdf_init, tsdf_table, tsdf_fuse, marching_tetrahedra, marching_tetrahedra_soup, index_soup
 from .knn import knn_points, knn_graph, KnnGraph, smooth_features, _SmoothFn
+from .hashgrid import hashgrid_levels, HashGridLevels, hashgrid_table, hashgrid_encode, hashgrid_forward, hashgrid_backward, _HashGridFn
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

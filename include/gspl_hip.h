@@ -1090,6 +1090,39 @@ int gspl_smooth_features_fwd(int N, int D, int K, uint32_t mask, const float* fe
 int gspl_smooth_features_bwd(int N, int D, int K, uint32_t mask, const float* features, const uint32_t* row_start, const uint32_t* entries,
                              const float* out, const float* mnorm, const float* v_out, float* v_features, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 20. Multiresolution hash-grid / dense-grid encoding for the SWAG route (csrc/hashgrid.hip).  PURELY ADDITIVE: two new entry
+ *    points, no new struct, nothing existing changes, GSPL_ABI_VERSION stays 39.  What `tinycudann.Encoding` with otype HashGrid or
+ *    DenseGrid and linear interpolation computes (internal/models/swag_model.py:75-78,98).  PARITY UNPINNED: there is no ROCm build of
+ *    tiny-cuda-nn to compare against; these are its published rules, and the fp64 oracle tests/hashgrid_oracle.py pins them here.
+ *
+ *  x [N,D] f32 (D = 2 or 3), F = 1, 2, 4 or 8 features per level, L = 1 .. 32 levels, table [offsets[L], F] f32, level-major.
+ *  The level table is computed ONCE ON THE HOST, in double, rounded once, and passed as HOST arrays (`ops.hashgrid_levels`):
+ *      scales[l]      = float32(exp2(l log2(per_level_scale)) base_resolution - 1)
+ *      resolutions[l] = ceil(scales[l]) + 1
+ *      size_l         = min(resolutions[l]^D, (2^32 - 1) / 2) rounded up to a multiple of 8; HashGrid: also capped at 2^log2_hashmap_size
+ *      offsets[l]     = running sum of the sizes ([L + 1]; offsets[l + 1] - offsets[l] = size_l <= 2^31, offsets[L] < 2^32)
+ *  A level is hashed iff resolutions[l]^D > size_l (derived here from the two arrays).
+ *  Per point and level:  pos_d = fmaf(x_d, scale_l, 0.5f) (ONE rounding);  cell_d = floor(pos_d) converted through int32 to uint32,
+ *  so negative and far inputs are legal and wrap;  frac_d = pos_d - floor(pos_d).  For each of the 2^D corners c (bit d of c selects
+ *  cell_d + 1): weight = product over d of (bit ? frac_d : 1 - frac_d); row = sum_d corner_d resolutions[l]^d (dense) or the XOR over d
+ *  of corner_d prime_d with primes (1, 2654435761, 805459861) (hashed), both in uint32, then mod size_l.
+ *      out[n, l F + f] = sum over corners of weight table[offsets[l] + row, f]
+ *  Every row index is reduced mod size_l, so no input value can address outside the table.
+ *
+ *  gspl_hashgrid_fwd: out [N, L F].  One launch, one level per blockIdx.y.
+ *  gspl_hashgrid_bwd: v_out [N, L F].  v_table (nullable) [offsets[L], F] is ACCUMULATED into (the caller clears it) with fp32
+ *    atomics: the sum depends on arrival order in the last bits.  Lanes of a wave whose consecutive points share a destination row are
+ *    summed before the atomic.  v_x (nullable; needs `table`) [N,D] is WRITTEN, without atomics:
+ *      v_x[n,d] = sum_l scale_l sum over corners of (+-1 on d) (product of the other dims' weights) <table row, v_out[n, l F ..]>
+ *    A (point, level) whose F values of v_out are all zero contributes nothing and is skipped before it reads x or the table.
+ *  table, out and v_out must be aligned to a row (4 F bytes, 16 from F = 4).  N == 0: no launch.
+ * ---------------------------------------------------------------------------------------- */
+int gspl_hashgrid_fwd(int N, int D, int F, int L, const float* scales, const uint32_t* resolutions, const uint32_t* offsets,
+                      const float* x, const float* table, float* out, void* stream);
+int gspl_hashgrid_bwd(int N, int D, int F, int L, const float* scales, const uint32_t* resolutions, const uint32_t* offsets,
+                      const float* x, const float* table, const float* v_out, float* v_table, float* v_x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
