@@ -130,7 +130,11 @@ int gspl_sh_fwd(int N, int degree,
 /*    v_dc / v_rest are written with the same strides (every coefficient of every Gaussian is
  *    written, zeros above the active degree / for masked rows, n_coeffs = number of coefficient
  *    rows present per Gaussian); v_dirs [N,3] nullable (gradient w.r.t. dirs, i.e. w.r.t. means
- *    when origin is used — the Inria path needs it, gsplat paths detach: gsplat_renderer.py:104). */
+ *    when origin is used — the Inria path needs it, gsplat paths detach: gsplat_renderer.py:104).
+ *    A row stride may be larger than the coefficients need; the backward then also writes 0 into the
+ *    columns between the last coefficient and the row stride of every v_rest row (of every merged row
+ *    when rest == dc + 3), so a caller must not keep other data there (a separate v_dc row gets its
+ *    three floats and nothing else). */
 int gspl_sh_bwd(int N, int degree, int n_coeffs,
                 const float* dirs, const float* origin /*nullable*/,
                 const float* dc, int dc_stride, const float* rest, int rest_stride,

@@ -77,6 +77,30 @@ def test_hip_vanilla_renderer_contract_and_parity():
     assert "depth" in d and d["depth"].shape == (3, cam["height"], cam["width"]) and float(d["depth"].detach().max()) > 0
 
 
+def test_hip_vanilla_renderer_convert_shs_python_matches_the_default_path():
+    """`convert_SHs_python=True`: the colours come from `ops.sh_view_colors(detach_means=False)` and enter the rasterizer as
+    `colors_precomp`; by default the rasterizer evaluates the SH itself.  Two formulations of one function in fp32 (in the fp64
+    oracle the two paths agree exactly): same image, same gradients — the means' includes the part through the view direction."""
+    import gspl_amd  # noqa: F401
+    from gspl_amd.renderers import HipVanillaRenderer
+    params, cam, wimg, bg = _scene()
+    camera = FakeCamera(cam, DEV)
+    target = torch.rand(3, cam["height"], cam["width"], generator=torch.Generator().manual_seed(9)).to(DEV)
+
+    def run(**kw):
+        model = FakeGaussianModel(*[p.to(DEV) for p in params])
+        out = HipVanillaRenderer(**kw)(camera, model, bg.to(DEV))
+        (out["render"] - target).abs().mean().backward()
+        return model, out
+
+    python, out_p = run(convert_SHs_python=True)
+    default, out_d = run()
+    assert torch.equal(out_p["radii"], out_d["radii"])
+    assert_pixels_close(out_p["render"].detach().cpu().numpy(), out_d["render"].detach().cpu().numpy(), name="convert_SHs_python render")
+    for name in ("means", "shs_dc", "shs_rest"):
+        assert_close_scaled(getattr(python, name).grad.cpu().numpy(), getattr(default, name).grad.cpu().numpy(), 1e-4, name)
+
+
 class _RawModel(torch.nn.Module):
     """Raw parameters behind exp / normalize / sigmoid getters, as the reference's VanillaGaussianModel keeps them
     (internal/models/vanilla_gaussian.py:345-358, 421-441), declaring so (renderer.model_raw_parameters)."""

@@ -123,9 +123,18 @@ def test_the_adaptive_switch_asks_for_a_tail_not_for_length():
             W, H = cam["width"], cam["height"]
             leaves = [t.to(DEV).requires_grad_(True) for t in params]
             m, s, q, o, c = leaves
+            # The verdict is remembered under the ADDRESS of the view matrix (a data set's cameras are persistent tensors).  The cameras of
+            # a test process are not: the allocator may hand this one the address under which an earlier test's view — any test that
+            # rendered a frame with a tail — left "tail", and the first frame here would then be segmented before anything was seen of
+            # this view.  So the matrix sits 16 bytes into a block of its own: no tensor's base (512-byte granules) and no row of a
+            # stack of 4x4 matrices (64-byte steps) has had that address.
+            block = torch.zeros(4 + 16, dtype=torch.float32, device=DEV)
+            viewmatrix = block[4:].view(4, 4)
+            viewmatrix.copy_(cam["world_to_camera"])
+            assert viewmatrix.data_ptr() % 64 == 16
             settings = ops.GaussianRasterizationSettings(
                 image_height=H, image_width=W, tanfovx=cam["tanfovx"], tanfovy=cam["tanfovy"], bg=torch.zeros(3, device=DEV), scale_modifier=1.0,
-                viewmatrix=cam["world_to_camera"].to(DEV), projmatrix=cam["full_projection"].to(DEV), sh_degree=3, campos=cam["camera_center"].to(DEV))
+                viewmatrix=viewmatrix, projmatrix=cam["full_projection"].to(DEV), sh_degree=3, campos=cam["camera_center"].to(DEV))
             on, longest, mean = [], 0, 0.0
             for _ in range(n):
                 render, radii = ops.GaussianRasterizer(settings)(means3D=m, means2D=torch.zeros_like(m, requires_grad=True), opacities=o, shs=c, scales=s, rotations=q)
