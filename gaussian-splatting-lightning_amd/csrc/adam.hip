@@ -18,6 +18,11 @@
 // 16-byte chunk whose rows all carry 0 does not LOAD its gradient: adam_elem runs on a zero that arrives as a kernel argument, the same
 // instructions on the same values.  Applied to tensors of at least GSPL_ADAM_ROWS_MIN floats per row, where whole cache lines of the
 // gradient go unread; the 1-4 float tensors touch most of their lines at any density and are read as always.
+//
+// Rows that never had a gradient (zero moments, zero gradient) are passed over: see selective_adam_kernel.
+#include <cmath>
+#include <cstdlib>
+
 #include "gspl_device.h"
 #include "gspl_host.h"
 
@@ -38,7 +43,13 @@ struct AdamBatchDev { AdamTensorDev t[GSPL_ADAM_MAX_TENSORS]; };
 #ifndef GSPL_ADAM_ROWS_MIN
 #define GSPL_ADAM_ROWS_MIN 32      // floats per row: one 128-byte line
 #endif
-template <bool ROWS>
+// No-op chunks (SKIP): a row no view has ever blended has m = v = +0 (as the optimizers create them) and g = +-0, and adam_elem then
+// gives m' = fma(b1, +0, (1 - b1) g) = +0, v' = +0, p' = p - (step * +0) / fma(0, inv_bc2, eps) = p - (+0) = p: the bits of all three stay
+// as they are for EVERY p (-0, denormals, inf, quiet NaN), provided eps > 0, b1 and b2 in [0, 1], step finite and >= +0 (a step of -0
+// would turn p = -0 into +0) and inv_bc2 finite — the host decides that once per launch (gspl_selective_adam_rows).  Such a chunk
+// loads neither p nor stores anything: m, v (and g, where it is read at all) arrive first, p follows for the chunks that are live.
+// m and v are compared as BITS: a moment of -0 is no no-op, the update turns it into +0.  Everything else runs the code it always ran.
+template <bool ROWS, bool SKIP>
 __global__ __launch_bounds__(256) void selective_adam_kernel(AdamBatchDev batch, int N, const uint8_t* __restrict__ visible,
                                                              float b1, float b2, float eps, float inv_bc1, float inv_bc2,
                                                              const uint8_t* __restrict__ grad_rows, float zero) {
@@ -49,8 +60,13 @@ __global__ __launch_bounds__(256) void selective_adam_kernel(AdamBatchDev batch,
     typedef float v4f __attribute__((ext_vector_type(4)));
     auto ntl = [](const float* base, int64_t i) { const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(base) + i); return make_float4(t.x, t.y, t.z, t.w); };
     auto nts = [](float* base, int64_t i, const float4& q) { v4f t = {q.x, q.y, q.z, q.w}; __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(base) + i); };
-    // two 16-byte chunks per thread and iteration (8 loads in flight) and streaming (nontemporal) accesses of everything that is
-    // not read again before the next step: 302 -> 257 us at 1 M Gaussians (1.65 GB: 6.4 TB/s)
+    // the dense form: two 16-byte chunks per thread and iteration (8 loads in flight) and streaming (nontemporal) accesses of everything
+    // that is not read again before the next step: 302 -> 257 us at 1 M Gaussians (1.65 GB: 6.4 TB/s).  The skipping form takes ONE
+    // chunk: a live chunk makes two dependent round trips, and what hides the second is other waves — 44 registers and 8 waves per SIMD
+    // against 79 and 6 with two chunks (three: 108 and 4, four: 134 and 3).  Measured at S-1080p-1M on one lease, the dense form at
+    // 239 us: 194 / 207 / 249 us with one / two / three chunks, 311 with four on another lease (profiles/adam_noop_rows.txt).  The
+    // loads keep the dense form's order (row flags, then g, m and v together): asking for m and v ahead of the flags was 5 - 8 us slower
+    constexpr int U = SKIP ? 1 : 2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     // the rows of a chunk with ONE division per chunk, a 32-bit one wherever the tensor has fewer than 2^31 elements (a chunk of 4
     // floats of a row of >= 32 lies in one row or two)
@@ -63,27 +79,38 @@ __global__ __launch_bounds__(256) void selective_adam_kernel(AdamBatchDev batch,
         else { r0 = e / T.row; rem = (int)(e - r0 * T.row); }
         return grad_rows[r0] != 0 || (rem + 3 >= T.row && grad_rows[r0 + 1] != 0);
     };
-    for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < nvec; i0 += 2 * stride) {
-        float4 p[2], g[2], m[2], v[2];
-        bool vis[2][4], any[2] = {false, false};
+    auto still = [](bool vis, float g, float m, float v) { return !vis || (((__float_as_uint(m) | __float_as_uint(v)) == 0u) && g == 0.f); };
+    for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < nvec; i0 += U * stride) {
+        float4 p[U], g[U], m[U], v[U];
+        bool vis[U][4], any[U];
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
+        for (int u = 0; u < U; ++u) {
             const int64_t i = i0 + u * stride;
+            any[u] = false;
             if (i < nvec) {
                 const int64_t e = i << 2;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { vis[u][k] = visible ? visible[(e + k) / T.row] != 0 : true; any[u] = any[u] || vis[u][k]; }
             }
             if (any[u]) {
-                p[u] = ntl(T.p, i);
+                if (!SKIP) p[u] = ntl(T.p, i);
                 if (!use_rows || has_grad(i << 2)) g[u] = ntl(T.g, i);
                 else g[u] = make_float4(zero, zero, zero, zero);
                 m[u] = ntl(T.m, i);
                 v[u] = ntl(T.v, i);
             }
         }
+        if (SKIP) {
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
+            for (int u = 0; u < U; ++u) {
+                if (!any[u]) continue;
+                if (still(vis[u][0], g[u].x, m[u].x, v[u].x) && still(vis[u][1], g[u].y, m[u].y, v[u].y) &&
+                    still(vis[u][2], g[u].z, m[u].z, v[u].z) && still(vis[u][3], g[u].w, m[u].w, v[u].w)) any[u] = false;
+                else p[u] = ntl(T.p, i0 + u * stride);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
             if (!any[u]) continue;
             const int64_t i = i0 + u * stride;
             if (vis[u][0]) adam_elem(p[u].x, g[u].x, m[u].x, v[u].x, step, b1, b2, inv_bc2, eps);
@@ -144,11 +171,20 @@ extern "C" int gspl_selective_adam_rows(int n_tensors, const gspl_adam_tensor* t
     // max_blocks > 0: a launch that runs NEXT TO other work (the deferred update on the colour stream) keeps to that many workgroups
     // per tensor, so that it leaves wave slots on every CU to the kernels of the other stream; the loop is grid-strided either way
     const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(want, max_blocks > 0 ? max_blocks : 16384));
-    if (grad_rows)
-        hipLaunchKernelGGL(selective_adam_kernel<true>, dim3(gx, n_tensors), dim3(256), 0, (hipStream_t)stream, b, N, visible,
-                           beta1, beta2, eps, 1.f / bias_correction1, 1.f / bias_correction2_sqrt, grad_rows, 0.f);
-    else
-        hipLaunchKernelGGL(selective_adam_kernel<false>, dim3(gx, n_tensors), dim3(256), 0, (hipStream_t)stream, b, N, visible,
-                           beta1, beta2, eps, 1.f / bias_correction1, 1.f / bias_correction2_sqrt, nullptr, 0.f);
+    // the range in which a chunk of zero moments and zero gradients is a no-op (the kernel's header); the products as the kernel forms them.
+    // GSPL_ADAM_SKIP_NOOP=0 (read once): every chunk takes the dense path — the same values, what the tests compare against
+    static const bool skip_enabled = [] { const char* e = getenv("GSPL_ADAM_SKIP_NOOP"); return !(e && e[0] == '0' && e[1] == 0); }();
+    const float inv_bc1 = 1.f / bias_correction1, inv_bc2 = 1.f / bias_correction2_sqrt;
+    bool skip = skip_enabled && eps > 0.f && beta1 >= 0.f && beta1 <= 1.f && beta2 >= 0.f && beta2 <= 1.f && std::isfinite(inv_bc2);
+    for (int k = 0; k < n_tensors && skip; ++k) {
+        const float step = tensors[k].lr * inv_bc1;
+        skip = std::isfinite(step) && step >= 0.f && !std::signbit(step);
+    }
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(gx, n_tensors), dim3(256), 0, (hipStream_t)stream, b, N, visible,
+                           beta1, beta2, eps, inv_bc1, inv_bc2, grad_rows, 0.f);
+    };
+    if (grad_rows) { if (skip) launch(selective_adam_kernel<true, true>); else launch(selective_adam_kernel<true, false>); }
+    else { if (skip) launch(selective_adam_kernel<false, true>); else launch(selective_adam_kernel<false, false>); }
     return check_launch("selective_adam");
 }
