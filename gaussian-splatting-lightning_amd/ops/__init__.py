@@ -30,6 +30,8 @@ reference's renderers call (same names, argument meaning and error behaviour):
       knn_points, knn_graph, KnnGraph, smooth_features
   SWAG's grid encoding (internal/models/swag_model.py:75-78, `tinycudann.Encoding` with otype HashGrid / DenseGrid)
       hashgrid_levels, HashGridLevels, hashgrid_table, hashgrid_encode, hashgrid_forward, hashgrid_backward
+  The appearance-embedding route's per-Gaussian MLP (internal/renderers/gsplat_appearance_embedding_renderer.py:50-93, `tcnn: false`)
+      appearance_mlp, appearance_mlp_check, appearance_mlp_forward, appearance_mlp_backward
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -65,6 +67,7 @@ from .envlight import cubemap_sample, envlight_blend, _CubemapFn, _BlendFn
 from .mesh import tsdf_init, tsdf_table, tsdf_fuse, marching_tetrahedra, marching_tetrahedra_soup, index_soup
 from .knn import knn_points, knn_graph, KnnGraph, smooth_features, _SmoothFn
 from .hashgrid import hashgrid_levels, HashGridLevels, hashgrid_table, hashgrid_encode, hashgrid_forward, hashgrid_backward, _HashGridFn
+from .appearance import appearance_mlp, appearance_mlp_check, appearance_mlp_forward, appearance_mlp_backward, _AppearanceMlpFn
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

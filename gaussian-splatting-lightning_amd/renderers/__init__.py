@@ -22,3 +22,4 @@ from .hip_feature_3dgs_renderer import HipFeature3DGSRenderer  # noqa: F401,E402
 from .hip_gsplat_contrastive_feature_renderer import HipGSplatContrastiveFeatureRenderer  # noqa: F401,E402
 from .hip_pvg_renderer import HipPeriodicVibrationGaussianRenderer, HipPeriodicVibrationGaussianRendererModule  # noqa: F401,E402
 from .hip_swag_renderer import HipSWAGRenderer  # noqa: F401,E402
+from .hip_gsplat_appearance_embedding_renderer import HipGSplatAppearanceEmbeddingRenderer, HipGSplatAppearanceEmbeddingRendererModule  # noqa: F401,E402

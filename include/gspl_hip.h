@@ -1127,6 +1127,40 @@ int gspl_hashgrid_fwd(int N, int D, int F, int L, const float* scales, const uin
 int gspl_hashgrid_bwd(int N, int D, int F, int L, const float* scales, const uint32_t* resolutions, const uint32_t* offsets,
                       const float* x, const float* table, const float* v_out, float* v_table, float* v_x, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 21. The per-Gaussian appearance MLP of the appearance-embedding route, fused (csrc/appearance.hip).  PURELY ADDITIVE: three new
+ *    entry points, no new struct, nothing existing changes, GSPL_ABI_VERSION stays 39.  What `Model.forward` of
+ *    internal/renderers/gsplat_appearance_embedding_renderer.py computes with `tcnn: false`, for the ONE embedding row of a call.
+ *    The reference's arithmetic is torch code, so it is pinned directly (tests/appearance_oracle.py); exact fp32 on the f32-input MFMA.
+ *
+ *  features [N,F] f32, F % 4 == 0, 4 <= F <= 128; embedding [E] f32, E <= 256; H = 32 or 64 hidden neurons; n_layers = 2 .. 4 linear
+ *  layers; n_out = 3 or 4; n_freq = 0 .. 8.  `weights` and `biases` are HOST arrays of n_layers DEVICE pointers in torch.nn.Linear
+ *  layout: weights[l] [out_l, in_l], biases[l] [out_l]; in_0 = F + E + P with P = n_freq ? 3 (2 n_freq + 1) : 0, the columns in the
+ *  order features | embedding | encoded direction; in_l = H after that; out_l = H but for the last, n_out.
+ *  flags: 1 = F.normalize (eps 1e-12) on each feature row and on the embedding; 2 = sigmoid on the output (else none).
+ *  n_freq > 0: d = (means[n] - camera_center) / max(|.|, 1e-12) (means [N,3], camera_center [3], both on the device), encoded as
+ *  d, sin(2^0 d), cos(2^0 d), sin(2^1 d), ...; d carries no gradient.  mask (nullable) [N] bytes: rows with 0 are not evaluated.
+ *      x = [f^ | e^ | enc(d)];  a_0 = relu(W_0 x + b_0);  ...;  out = act(W_last a + b_last)
+ *  The embedding is folded into the first bias once per workgroup: b_0' = b_0 + W_0[:, F:F+E] e^.
+ *
+ *  gspl_appearance_mlp_fwd: out [N, n_out], every row WRITTEN (masked rows: zeros).
+ *  gspl_appearance_mlp_bwd: v_out [N, n_out] (masked rows are not read).  v_features (nullable) [N,F], 16-byte aligned: every row
+ *    WRITTEN (masked rows: zeros).  v_params (nullable): the gradients in the parameters' own layout, every element WRITTEN,
+ *        [W_0 | b_0 | W_1 | b_1 | ... | embedding [E]]
+ *    Hidden activations are recomputed.  Rows are assigned to workgroups statically, each workgroup writes one partial into
+ *    `workspace` (gspl_appearance_mlp_workspace_bytes), and a second launch sums the partials in workgroup order: no float atomics,
+ *    the same bits on every run.  v_params == NULL: no weight-gradient arithmetic, no second launch, no workspace.
+ *  A network whose LDS images do not fit 160 KiB is refused.  N == 0: no launch (v_params is cleared).
+ * ---------------------------------------------------------------------------------------- */
+size_t gspl_appearance_mlp_workspace_bytes(int N, int F, int E, int H, int n_layers, int n_out, int n_freq);
+int gspl_appearance_mlp_fwd(int N, int F, int E, int H, int n_layers, int n_out, int n_freq, int flags, const float* features,
+                            const uint8_t* mask, const float* means, const float* camera_center, const float* embedding,
+                            const float* const* weights, const float* const* biases, float* out, void* stream);
+int gspl_appearance_mlp_bwd(int N, int F, int E, int H, int n_layers, int n_out, int n_freq, int flags, const float* features,
+                            const uint8_t* mask, const float* means, const float* camera_center, const float* embedding,
+                            const float* const* weights, const float* const* biases, const float* v_out, float* v_features,
+                            float* v_params, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
