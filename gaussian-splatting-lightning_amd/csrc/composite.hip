@@ -6,6 +6,12 @@
 // Neither CUDA package is vendored in the reference; the algorithm restated here is the published
 // 3DGS compositing rule with the per-API constants of SURVEY.md Appendix B (ModeTraits).
 // Roofline: algorithmic bytes 40*I + 20*P; VALU/exp-bound under that model — bench.py reports both fractions.
+//
+// Both kernels walk a list with one wave per 8x8 block; the walk — block derivation, the round's compaction, the per-pixel alpha
+// and the blending decision — is defined once in gspl_composite.h ("the 8x8 block walk").  composite_fwd_kernel takes the block
+// and the blending decision from there and specialises the round (its own gather with a prefetch and the colours, a padding entry,
+// no wave barriers) and the per-pixel alpha (two candidates at a time, packed); composite_scores_kernel uses all four pieces and
+// specialises only what it does with a blended pair.
 #include "gspl_composite.h"
 
 namespace gspl {
@@ -19,7 +25,7 @@ namespace gspl {
 // Per round of 64 splats:
 //   1. lane l gathers splat base+l and tests ITS splat's alpha >= 1/255 box against the quadrant;
 //   2. ballot + prefix count (v_mbcnt) COMPACT the candidates into a structure-of-arrays list in LDS
-//      (x[], y[], ha[], b[], hc[], opacity[], colour[][D]);
+//      (x[], y[], ha[], k[], hd[], opacity[], list position[], colour[][D]) — compact_round's compaction, written out here;
 //   3. the wave walks the list TWO candidates at a time: one ds_read_b64 per array yields the pair as a
 //      64-bit register pair, so sigma / exp argument / alpha are evaluated with packed fp32 math
 //      (v_pk_add/mul/fma_f32: half the instructions — and issue slots, scalar bookkeeping — for the same arithmetic),
@@ -50,19 +56,14 @@ __global__ __launch_bounds__(64) void composite_fwd_kernel(
     __shared__ __attribute__((aligned(16))) int s_pos[FLIST];      // list index (base + lane) of each candidate
     __shared__ __attribute__((aligned(16))) float s_col[FLIST * D];
 
-    const int unit = xcd_remap(blockIdx.x, 4 * n_tiles, 4 * GSPL_XCD_RUN);     // (tile, quadrant): the four quadrants of a tile stay on one XCD
-    const int tile = unit >> 2, w = unit & 3, l = threadIdx.x;
-    const int px = (tile % tile_w) * TILE + (w & 1) * 8 + (l & 7);
-    const int py = (tile / tile_w) * TILE + (w >> 1) * 8 + (l >> 3);
+    // (tile, quadrant): the four quadrants of a tile stay on one XCD
+    const WalkBlock b = walk_block<MODE>(xcd_remap(blockIdx.x, 4 * n_tiles, 4 * GSPL_XCD_RUN), tile_w);
+    const int w = b.w, l = threadIdx.x, px = b.px, py = b.py;
     const bool inside = (px < width) && (py < height);
-    const float pxf = (float)px + TR::kPixelCentre, pyf = (float)py + TR::kPixelCentre;
-    const v2f pxf2 = {pxf, pxf}, pyf2 = {pyf, pyf};
-    // pixel-centre bounds of this wave's 8x8 quadrant (wave-uniform)
-    const float qx0 = (float)((tile % tile_w) * TILE + (w & 1) * 8) + TR::kPixelCentre, qx1 = qx0 + 7.f;
-    const float qy0 = (float)((tile / tile_w) * TILE + (w >> 1) * 8) + TR::kPixelCentre, qy1 = qy0 + 7.f;
+    const v2f pxf2 = {b.pxf, b.pxf}, pyf2 = {b.pyf, b.pyf};
 
     int start, end;      // the list of the LIST tile this 8x8 block lies in (n_tiles / tile_w are the 16x16 compute grid)
-    block_list_range(lt, (tile % tile_w) * 2 + (w & 1), (tile / tile_w) * 2 + (w >> 1), width, height, n_isects, offsets, start, end);
+    block_list_range(lt, b.bx, b.by, width, height, n_isects, offsets, start, end);
 
     zero_table(seg.zero_p, seg.zero_n16);      // the backward's packed rows (this kernel waits for VALU issue: the stores ride for free)
     if (seg.walk && blockIdx.x == 0) {
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(64) void composite_fwd_kernel(
             if (i < end) {
                 ca = conics[g * 3 + 0]; cb = conics[g * 3 + 1]; cc = conics[g * 3 + 2]; op = opacities[g];
                 xy = make_float2(means2d[g * 2 + 0], means2d[g * 2 + 1]);
-                cand = box_reachable(xy.x, xy.y, ca, cb, cc, op, qx0, qx1, qy0, qy1);
+                cand = box_reachable(xy.x, xy.y, ca, cb, cc, op, b.qx0, b.qx1, b.qy0, b.qy1);
             }
             const unsigned long long mask = __ballot(cand);
             const int ncand = __builtin_popcountll(mask);
@@ -152,16 +153,11 @@ __global__ __launch_bounds__(64) void composite_fwd_kernel(
                 const int pos[2] = {pos2.x, pos2.y};
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
-                    const bool valid = !done && (sig[e] >= 0.f) && (alpha[e] >= kAlphaMin);
-                    const float next_T = T * (1.f - alpha[e]);
-                    const bool stop = valid && (TR::kStopInclusive ? (next_T <= kTStop) : (next_T < kTStop));
-                    const bool contrib = valid && !stop;
-                    const float wgt = contrib ? alpha[e] * T : 0.f;
+                    float wgt;
+                    const bool contrib = blend_step<MODE>(sig[e], alpha[e], T, done, wgt);
 #pragma unroll
                     for (int c = 0; c < D; ++c) acc[c] = fmaf(s_col[(k + e) * D + c], wgt, acc[c]);
-                    T = contrib ? next_T : T;
                     last = contrib ? pos[e] : last;
-                    done = done || stop;
                     if constexpr (HITS) hitmask |= (__ballot(contrib) != 0ull ? 1ull : 0ull) << (k + e);
                 }
                 if (__all(done)) { all_done = true; break; }
@@ -235,55 +231,31 @@ __global__ __launch_bounds__(64) void composite_scores_kernel(
     const int32_t* __restrict__ offsets, const int32_t* __restrict__ flatten_ids, const float* __restrict__ pixel_weights,
     int32_t* __restrict__ count, float* __restrict__ opacity_sum, float* __restrict__ alpha_sum, float* __restrict__ vis_sum,
     float* __restrict__ weighted_sum, float* __restrict__ dist_sum) {
-    using TR = ModeTraits<MODE>;
-    __shared__ float s_x[64], s_y[64], s_ha[64], s_k[64], s_hd[64], s_op[64];
+    __shared__ RoundLists s;
     __shared__ int s_g[64];
-    const int unit = blockIdx.x;
-    const int tile = unit >> 2, w = unit & 3, l = threadIdx.x;
-    const int px = (tile % tile_w) * TILE + (w & 1) * 8 + (l & 7);
-    const int py = (tile / tile_w) * TILE + (w >> 1) * 8 + (l >> 3);
-    const bool inside = (px < width) && (py < height);
-    const float pxf = (float)px + TR::kPixelCentre, pyf = (float)py + TR::kPixelCentre;
-    const float qx0 = (float)((tile % tile_w) * TILE + (w & 1) * 8) + TR::kPixelCentre, qx1 = qx0 + 7.f;
-    const float qy0 = (float)((tile / tile_w) * TILE + (w >> 1) * 8) + TR::kPixelCentre, qy1 = qy0 + 7.f;
-    const float wpx = (pixel_weights && inside) ? pixel_weights[(int64_t)py * width + px] : 0.f;
-    int start, end;
-    tile_range(tile, n_tiles, n_isects, offsets, start, end);
+    const int l = threadIdx.x;
+    const WalkBlock b = walk_block<MODE>(blockIdx.x, tile_w);
+    const bool inside = (b.px < width) && (b.py < height);
+    const float wpx = (pixel_weights && inside) ? pixel_weights[(int64_t)b.py * width + b.px] : 0.f;
+    int start, end;      // (list tiles = compute tiles here: the host refuses every other tile_size)
+    tile_range(blockIdx.x >> 2, n_tiles, n_isects, offsets, start, end);
     float T = 1.f;
     bool done = !inside;
     for (int base = start; base < end && !__all(done); base += 64) {
-        const int i = base + l;
-        bool cand = false;
-        float mx = 0.f, my = 0.f, ca = 0.f, cb = 0.f, cc = 0.f, op = 0.f;
-        int g = 0;
-        if (i < end) {
-            g = flatten_ids[i];
-            ca = conics[g * 3 + 0]; cb = conics[g * 3 + 1]; cc = conics[g * 3 + 2]; op = opacities[g];
-            mx = means2d[g * 2 + 0]; my = means2d[g * 2 + 1];
-            cand = box_reachable(mx, my, ca, cb, cc, op, qx0, qx1, qy0, qy1);
-        }
-        const unsigned long long mask = __ballot(cand);
-        const int ncand = __builtin_popcountll(mask);
-        const int slot = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+        const bool has = base + l < end;
+        const int g = has ? flatten_ids[base + l] : 0;
+        const RoundSlot r = compact_round(has, g, means2d, conics, opacities, b, s);
+        if (r.cand) s_g[r.slot] = g;
         __builtin_amdgcn_wave_barrier();
-        if (cand) {
-            const SigmaCoef sc = sigma_coef(ca, cb, cc);
-            s_x[slot] = mx; s_y[slot] = my; s_ha[slot] = sc.ha; s_k[slot] = sc.k; s_hd[slot] = sc.hd; s_op[slot] = op; s_g[slot] = g;
-        }
-        __builtin_amdgcn_wave_barrier();
-        for (int k = 0; k < ncand; ++k) {
-            const float dx = s_x[k] - pxf, dy = s_y[k] - pyf, o = s_op[k];
-            // the compositing kernels' own expression tree (eval_sigma, exp2 of the scaled argument): the same pairs are counted as blended
-            const float sigma = eval_sigma(s_ha[k], s_k[k], s_hd[k], dx, dy);
-            const float alpha = fminf(TR::kAlphaMax, o * __builtin_amdgcn_exp2f(sigma * -1.4426950408889634f));
-            const bool valid = !done && (sigma >= 0.f) && (alpha >= kAlphaMin);
-            const float next_T = T * (1.f - alpha);
-            const bool stop = valid && (TR::kStopInclusive ? (next_T <= kTStop) : (next_T < kTStop));
-            const bool contrib = valid && !stop;
+        for (int k = 0; k < r.ncand; ++k) {
+            const PixelAlpha pa = pixel_alpha(s, k, b.pxf, b.pyf);
+            const float alpha = clamp_alpha<MODE>(pa.raw), o = s.op[k];
+            float v;
+            const bool contrib = blend_step<MODE>(pa.sigma, alpha, T, done, v);
             const unsigned long long hit = __ballot(contrib);
             if (hit) {
-                float a = contrib ? alpha : 0.f, v = contrib ? alpha * T : 0.f;
-                float wv = v * wpx, ds = contrib ? sqrtf(dx * dx + dy * dy) : 0.f;
+                float a = contrib ? alpha : 0.f;
+                float wv = v * wpx, ds = contrib ? sqrtf(pa.dx * pa.dx + pa.dy * pa.dy) : 0.f;
 #pragma unroll
                 for (int d = 32; d > 0; d >>= 1) {
                     a += __shfl_xor(a, d); v += __shfl_xor(v, d); wv += __shfl_xor(wv, d); ds += __shfl_xor(ds, d);
@@ -299,8 +271,6 @@ __global__ __launch_bounds__(64) void composite_scores_kernel(
                     if (dist_sum) atomicAdd(dist_sum + gk, ds);
                 }
             }
-            T = contrib ? next_T : T;
-            done = done || stop;
             if (__all(done)) break;
         }
     }
@@ -343,10 +313,10 @@ int gspl::composite_fwd_impl(int N, int D, int mode, int layout, const Composite
     if (lists.n_isects != 0 && (!sp.means2d || !sp.conics || !sp.colors || !sp.opacities || !lists.flatten_ids)) return fail_arg("composite_fwd: NULL required pointer");
     // the kernel walks 8x8 blocks grouped into 16x16 compute tiles; the lists are those of the caller's tile_size (8, 16 or 32)
     const ListTiles lt = list_tiles(grid);
-    const int ctw = (image.width + TILE - 1) / TILE, n_tiles = ctw * ((image.height + TILE - 1) / TILE);
+    const ComputeTiles ct = compute_tiles(image);
     hipStream_t s = (hipStream_t)stream;
     return dispatch_composite(D, mode, layout, [&](auto d, auto m, auto chw) {
-        return launch_fwd<d(), m(), chw()>(n_tiles, ctw, image, sp, lists, out_colors, out_alphas, final_Ts, last_ids, hit_flags, s, lt, seg);
+        return launch_fwd<d(), m(), chw()>(ct.n, ct.w, image, sp, lists, out_colors, out_alphas, final_Ts, last_ids, hit_flags, s, lt, seg);
     });
 }
 

@@ -419,9 +419,10 @@ __global__ __launch_bounds__(B2_NT, GSPL_BWD2_WAVES) void composite_bwd2_kernel(
 // ---------------------------------------------------------------------------------------------------------------
 // Backward for tile lists cut on 8- or 32-pixel tiles (`tile_size` 8 / 32 of the callers, gsplat_v1_renderer.py:23-41): ONE WAVE
 // PER 8x8 BLOCK, one pixel per lane, the block walks the list of the list tile that holds it (gspl_composite.h, ListTiles) back
-// to front.  Per round of 64 list entries the lanes cull their entry against the block (box_reachable) and compact the candidates
-// with ballot + mbcnt (ascending lane = descending list index); per candidate every lane evaluates its pixel (the same expression
-// tree as composite_bwd2_kernel), the NV values are summed over the wave with DPP and lane 63 issues the L2 atomics.  The same
+// to front.  The walk is the 8x8 block walk of gspl_composite.h: per round of 64 list entries compact_round culls and compacts the
+// candidates (ascending lane = descending list index) and this kernel stages the list index, the splat, its colours and the conic's b
+// and c / 2 beside them; per candidate every lane evaluates its pixel (pixel_alpha: the same expression tree as
+// composite_bwd2_kernel), the NV values are summed over the wave with DPP and lane 63 issues the L2 atomics.  The same
 // arithmetic and the same discrete decisions as the 16-pixel path; a compatibility path, correct before fast (the default tile size
 // of every configuration of the reference is 16).
 template <int D, int MODE, bool CHW, bool ABS, bool PACKED>
@@ -437,21 +438,18 @@ __global__ __launch_bounds__(64) void composite_bwd_block_kernel(
     uint8_t* __restrict__ hit_flags, ListTiles lt) {
     using TR = ModeTraits<MODE>;
     constexpr int NV = BwdVals<D, ABS>::N;
-    __shared__ float s_x[64], s_y[64], s_ha[64], s_b[64], s_hc[64], s_op[64], s_k[64], s_hd[64];
+    __shared__ RoundLists s;
+    __shared__ float s_b[64], s_hc[64];      // the conic's b and c / 2: with ha, what turns the moments into gradients
     __shared__ float s_col[64 * D];
     __shared__ int s_g[64], s_idx[64];
 
-    const int unit = xcd_remap(blockIdx.x, 4 * n_tiles, 4 * GSPL_XCD_RUN);
-    const int tile = unit >> 2, w = unit & 3, l = threadIdx.x;
-    const int bx = (tile % tile_w) * 2 + (w & 1), by = (tile / tile_w) * 2 + (w >> 1);
-    const int px = bx * 8 + (l & 7), py = by * 8 + (l >> 3);
-    const bool inside = (px < width) && (py < height);
-    const float pxf = (float)px + TR::kPixelCentre, pyf = (float)py + TR::kPixelCentre;
-    const float qx0 = (float)(bx * 8) + TR::kPixelCentre, qy0 = (float)(by * 8) + TR::kPixelCentre;
+    const int l = threadIdx.x;
+    const WalkBlock blk = walk_block<MODE>(xcd_remap(blockIdx.x, 4 * n_tiles, 4 * GSPL_XCD_RUN), tile_w);
+    const bool inside = (blk.px < width) && (blk.py < height);
     int start, end;
-    block_list_range(lt, bx, by, width, height, n_isects, offsets, start, end);
+    block_list_range(lt, blk.bx, blk.by, width, height, n_isects, offsets, start, end);
 
-    const int64_t pix = (int64_t)py * width + px;
+    const int64_t pix = (int64_t)blk.py * width + blk.px;
     const int last = inside ? last_ids[pix] : start;
     float T = inside ? final_Ts[pix] : 1.f;
     float vo[D];
@@ -468,39 +466,25 @@ __global__ __launch_bounds__(64) void composite_bwd_block_kernel(
 
     for (int hi = block_last; hi > start; hi -= 64) {
         const int idx = hi - 1 - l;                 // lane 0 = the deepest entry of the round
-        bool cand = false;
-        int g = 0;
-        float mx = 0.f, my = 0.f, ca = 0.f, cb = 0.f, cc = 0.f, op = 0.f;
-        if (idx >= start) {
-            g = flatten_ids[idx];
-            ca = conics[g * 3 + 0]; cb = conics[g * 3 + 1]; cc = conics[g * 3 + 2]; op = opacities[g];
-            mx = means2d[g * 2 + 0]; my = means2d[g * 2 + 1];
-            cand = box_reachable(mx, my, ca, cb, cc, op, qx0, qx0 + 7.f, qy0, qy0 + 7.f);
-        }
-        const unsigned long long mask = __ballot(cand);
-        const int ncand = __builtin_popcountll(mask);
-        const int slot = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-        __syncthreads();
-        if (cand) {
-            const SigmaCoef sc = sigma_coef(ca, cb, cc);
-            s_x[slot] = mx; s_y[slot] = my; s_ha[slot] = sc.ha; s_b[slot] = cb; s_hc[slot] = 0.5f * cc; s_op[slot] = op;
-            s_k[slot] = sc.k; s_hd[slot] = sc.hd;
-            s_g[slot] = g; s_idx[slot] = idx;
+        const bool has = idx >= start;
+        const int g = has ? flatten_ids[idx] : 0;
+        const RoundSlot r = compact_round(has, g, means2d, conics, opacities, blk, s);
+        if (r.cand) {
+            s_b[r.slot] = r.b; s_hc[r.slot] = 0.5f * r.c;
+            s_g[r.slot] = g; s_idx[r.slot] = idx;
 #pragma unroll
-            for (int c = 0; c < D; ++c) s_col[slot * D + c] = colors[(int64_t)g * D + c];
+            for (int c = 0; c < D; ++c) s_col[r.slot * D + c] = colors[(int64_t)g * D + c];
         }
         __syncthreads();
-        for (int k = 0; k < ncand; ++k) {
+        for (int k = 0; k < r.ncand; ++k) {
             const int kidx = s_idx[k];
-            const float ha = s_ha[k], b = s_b[k], hc = s_hc[k], o = s_op[k];
-            const float dx = s_x[k] - pxf, dy = s_y[k] - pyf;
-            const float sigma = eval_sigma(ha, s_k[k], s_hd[k], dx, dy);
-            const float vis = __builtin_amdgcn_exp2f(sigma * -1.4426950408889634f);
-            const float raw = o * vis;
-            const bool valid = (kidx < last) && (sigma >= 0.f) && (raw >= kAlphaMin);
+            const float ha = s.ha[k], b = s_b[k], hc = s_hc[k], o = s.op[k];
+            const PixelAlpha pa = pixel_alpha(s, k, blk.pxf, blk.pyf);
+            const float dx = pa.dx, dy = pa.dy;
+            const bool valid = alpha_test(kidx < last, pa.sigma, pa.raw);      // (the clamp does not move the 1/255 test)
             if (!__any(valid)) continue;
-            const float rv = valid ? raw : 0.f;
-            const float a = fminf(TR::kAlphaMax, rv);
+            const float rv = valid ? pa.raw : 0.f;
+            const float a = clamp_alpha<MODE>(rv);
             float rw = rv;
             if (TR::kClampKillsGrad) rw = (rv <= TR::kAlphaMax) ? rv : 0.f;
             const float om = 1.f - a;
@@ -621,11 +605,11 @@ extern "C" int gspl_composite_bwd(int N, int64_t n_isects, int D, int mode, int 
         !v_out_colors || !v_means2d || !v_conics || !v_colors || !v_opacities)
         return fail_arg("composite_bwd: NULL required pointer");
     const ListTiles lt = list_tiles(grid);
-    const int ctw = (width + TILE - 1) / TILE, n_tiles = ctw * ((height + TILE - 1) / TILE);      // 16x16 compute tiles
+    const ComputeTiles ct = compute_tiles(image);
     hipStream_t s = (hipStream_t)stream;
     const bool absgrad = v_means2d_abs != nullptr;
     return dispatch_composite(D, mode, layout, [&](auto d, auto m, auto chw) {
-        return launch_bwd<d(), m(), chw()>(absgrad, n_tiles, ctw, image, CompositeSplats{means2d, conics, colors, opacities, backgrounds},
+        return launch_bwd<d(), m(), chw()>(absgrad, ct.n, ct.w, image, CompositeSplats{means2d, conics, colors, opacities, backgrounds},
                                            TileLists{offsets, flatten_ids, n_isects}, final_Ts, last_ids, v_out_colors, v_out_alphas, v_means2d, v_means2d_abs, v_conics, v_colors, v_opacities, s, 0,
                                            hit_flags, lt);
     });
@@ -731,7 +715,7 @@ int gspl::composite_bwd_packed_impl(int N, int D, int mode, int layout, const Co
     if (!sp.means2d || !sp.conics || !sp.colors || !sp.opacities || !lists.offsets || !lists.flatten_ids || !final_Ts || !last_ids || !v_out_colors || !v_packed)
         return fail_arg("composite_bwd_packed: NULL required pointer");
     const ListTiles lt = list_tiles(grid);
-    const int ctw = (image.width + TILE - 1) / TILE, n_tiles = ctw * ((image.height + TILE - 1) / TILE);      // 16x16 compute tiles
+    const ComputeTiles ct = compute_tiles(image);
     hipStream_t s = (hipStream_t)stream;
     const bool ag = absgrad != 0;
     // deterministic mode (see gspl_set_deterministic below): rows per list entry, then an ordered reduction per splat
@@ -750,7 +734,7 @@ int gspl::composite_bwd_packed_impl(int N, int D, int mode, int layout, const Co
         seg = nullptr;      // (rows per list entry, one writer each: the plain walk)
     }
     rc = dispatch_composite(D, mode, layout, [&](auto d, auto m, auto chw) {
-        return launch_bwd<d(), m(), chw(), true>(ag, n_tiles, ctw, image, sp, lists,
+        return launch_bwd<d(), m(), chw(), true>(ag, ct.n, ct.w, image, sp, lists,
                                                  final_Ts, last_ids, v_out_colors, v_out_alphas, v_packed, nullptr, nullptr, nullptr, nullptr, s, packed_stride,
                                                  hit_flags, lt, seg, fill);
     });

@@ -5,13 +5,14 @@
 // (internal/renderers/gsplat_contrastive_feature_renderer.py: 32) composite many channels over a FROZEN model: the blending weights
 // alpha T do not depend on the channel and no geometry gradient is asked for.  The kernels of composite.hip are built for D <= 8 and a
 // backward that reduces 6 + D values per (tile, splat); here the cost per channel is one multiply-add per (pixel, splat):
-//   * feature_fwd_kernel: composite_fwd_kernel's decomposition (one wave per 8x8 block, lane = pixel, rounds of 64 list entries compacted
-//     into LDS), CH channels in registers per workgroup, the chunks of CH on grid.y.  Every chunk re-evaluates the weights (~20 VALU
-//     instructions per candidate against CH multiply-adds); chunk 0 writes alpha, T and last_ids.  Per channel the sum is the fmaf chain
-//     of composite_fwd_kernel in list order, with the one sigma / alpha definition of gspl_composite.h: the image is bit-for-bit the one
-//     the narrow kernels give channel by channel.
-//   * feature_bwd_kernel: v_features[g, c] += sum_pixels (alpha T) v_out[pixel, c].  Front to back up to last_ids, T recomputed with the
-//     forward's expressions.  The sum over the block's 64 pixels is a TRANSPOSE, not a cross-lane reduction: phase 1 (lane = pixel)
+//   * feature_fwd_kernel: the 8x8 block walk of gspl_composite.h (one wave per 8x8 block, lane = pixel, rounds of 64 list entries compacted
+//     into LDS: walk_block, compact_round, pixel_alpha, blend_step — the definitions composite_fwd_kernel takes its decisions with), CH
+//     channels in registers per workgroup, the chunks of CH on grid.y.  Every chunk re-evaluates the weights (~20 VALU instructions per
+//     candidate against CH multiply-adds); chunk 0 writes alpha, T and last_ids.  Per channel the sum is the fmaf chain of
+//     composite_fwd_kernel in list order: the image is bit-for-bit the one the narrow kernels give channel by channel.  What is this
+//     kernel's own: the list position and splat id staged beside the round's common arrays, the feature rows, the channel sums.
+//   * feature_bwd_kernel: v_features[g, c] += sum_pixels (alpha T) v_out[pixel, c].  The same walk front to back up to last_ids, T
+//     recomputed with the forward's expressions (pixel_alpha; alpha_test behind "not behind this pixel's last contributor").  The sum over the block's 64 pixels is a TRANSPOSE, not a cross-lane reduction: phase 1 (lane = pixel)
 //     leaves the round's weights W[candidate][pixel] in LDS; phase 2 (lane = channel) holds its channel's 64 v_out values in registers
 //     and accumulates sum_p W[k][p] v[p], W arriving as LDS broadcasts (one ds_read_b128 per four multiply-adds).  Lane c then owns
 //     (k, c): one fp32 atomic per (block, splat, channel), 64 consecutive channels of one splat row per instruction.  Up to 32 channels
@@ -26,69 +27,6 @@ constexpr int kRound = 64;               // list entries per round = lanes
 constexpr int kWStride = 64;             // W[candidate][pixel]: rows of 64 floats (16-byte aligned reads of four pixels)
 constexpr int kVStride = 65;             // the CHW staging of v_out, [channel][pixel]: odd stride, lane = channel reads hit 64 banks
 
-struct FeatureBlock {
-    int px, py, start, end;
-    bool inside;
-    float pxf, pyf, qx0, qx1, qy0, qy1;
-};
-
-// The 8x8 block of workgroup blockIdx.x and its list, exactly as composite_fwd_kernel derives them.  `empty`: no list exists (N == 0 or
-// no intersections) and `offsets` is not read.
-template <int MODE>
-__device__ __forceinline__ FeatureBlock feature_block(int n_tiles, int tile_w, int width, int height, int64_t n_isects, bool empty,
-                                                      const int32_t* __restrict__ offsets, const ListTiles& lt) {
-    using TR = ModeTraits<MODE>;
-    FeatureBlock b;
-    const int unit = xcd_remap(blockIdx.x, 4 * n_tiles, 4 * GSPL_XCD_RUN);
-    const int tile = unit >> 2, w = unit & 3, l = threadIdx.x;
-    const int bx = (tile % tile_w) * 2 + (w & 1), by = (tile / tile_w) * 2 + (w >> 1);
-    b.px = bx * 8 + (l & 7);
-    b.py = by * 8 + (l >> 3);
-    b.inside = (b.px < width) && (b.py < height);
-    b.pxf = (float)b.px + TR::kPixelCentre;
-    b.pyf = (float)b.py + TR::kPixelCentre;
-    b.qx0 = (float)(bx * 8) + TR::kPixelCentre; b.qx1 = b.qx0 + 7.f;
-    b.qy0 = (float)(by * 8) + TR::kPixelCentre; b.qy1 = b.qy0 + 7.f;
-    b.start = b.end = 0;
-    if (!empty) block_list_range(lt, bx, by, width, height, n_isects, offsets, b.start, b.end);
-    return b;
-}
-
-// One round's candidates, compacted: lane l tests list entry base + l against the block and the survivors land in slots 0 .. ncand - 1 in
-// list order.  Returns ncand.
-struct RoundLists {
-    float* x; float* y; float* ha; float* k; float* hd; float* op; int* pos; int* g;
-};
-__device__ __forceinline__ int compact_round(const FeatureBlock& b, int base, int g, const float* __restrict__ means2d,
-                                             const float* __restrict__ conics, const float* __restrict__ opacities, const RoundLists& s) {
-    const int l = threadIdx.x, i = base + l;
-    bool cand = false;
-    float mx = 0.f, my = 0.f, ca = 0.f, cb = 0.f, cc = 0.f, op = 0.f;
-    if (i < b.end) {
-        ca = conics[g * 3 + 0]; cb = conics[g * 3 + 1]; cc = conics[g * 3 + 2]; op = opacities[g];
-        mx = means2d[g * 2 + 0]; my = means2d[g * 2 + 1];
-        cand = box_reachable(mx, my, ca, cb, cc, op, b.qx0, b.qx1, b.qy0, b.qy1);
-    }
-    const unsigned long long mask = __ballot(cand);
-    const int slot = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-    __builtin_amdgcn_wave_barrier();
-    if (cand) {
-        const SigmaCoef sc = sigma_coef(ca, cb, cc);
-        s.x[slot] = mx; s.y[slot] = my; s.ha[slot] = sc.ha; s.k[slot] = sc.k; s.hd[slot] = sc.hd; s.op[slot] = op;
-        s.pos[slot] = i + 1; s.g[slot] = g;
-    }
-    __builtin_amdgcn_wave_barrier();
-    return __builtin_popcountll(mask);
-}
-
-// alpha of candidate k at this lane's pixel: the expression tree of composite_fwd_kernel (eval_sigma2's components are eval_sigma)
-template <int MODE>
-__device__ __forceinline__ float candidate_alpha(const FeatureBlock& b, const RoundLists& s, int k, float& sigma) {
-    const float dx = s.x[k] - b.pxf, dy = s.y[k] - b.pyf;
-    sigma = eval_sigma(s.ha[k], s.k[k], s.hd[k], dx, dy);
-    return fminf(ModeTraits<MODE>::kAlphaMax, s.op[k] * __builtin_amdgcn_exp2f(sigma * -1.4426950408889634f));
-}
-
 // acc + T bg as the narrow kernels round it.  composite_fwd_kernel writes `acc[c] + T * bgc`, and what hipcc makes of it is part of
 // the bits its callers see: in every instantiation (D = 1, 2, 3, 4, 8; both modes and layouts) the channels are finished in pairs, the
 // even one by a fused multiply-add, the odd one by a rounded product and an add.  The channel adapter cuts on multiples of 8, so the
@@ -100,11 +38,6 @@ __device__ __forceinline__ float add_background(float acc, float T, float bg, bo
     return even_channel ? fmaf(T, bg, acc) : acc + product;
 }
 
-#define GSPL_FEATURE_LISTS()                                                                                             \
-    __shared__ float s_x[kRound], s_y[kRound], s_ha[kRound], s_k[kRound], s_hd[kRound], s_op[kRound];                    \
-    __shared__ int s_pos[kRound], s_g[kRound];                                                                           \
-    const RoundLists s = {s_x, s_y, s_ha, s_k, s_hd, s_op, s_pos, s_g}
-
 template <int CH, int MODE, bool CHW>
 __global__ __launch_bounds__(64) void feature_fwd_kernel(
     int n_tiles, int tile_w, int width, int height, int64_t n_isects, int D, bool empty,
@@ -112,25 +45,31 @@ __global__ __launch_bounds__(64) void feature_fwd_kernel(
     const float* __restrict__ opacities, const float* __restrict__ backgrounds,
     const int32_t* __restrict__ offsets, const int32_t* __restrict__ flatten_ids,
     float* __restrict__ out, float* __restrict__ out_alphas, float* __restrict__ final_Ts, int32_t* __restrict__ last_ids, ListTiles lt) {
-    using TR = ModeTraits<MODE>;
-    GSPL_FEATURE_LISTS();
+    __shared__ RoundLists s;
+    __shared__ int s_pos[kRound], s_g[kRound];      // list index + 1 and splat of each candidate
     __shared__ __attribute__((aligned(16))) float s_f[kRound * CH];      // [candidate][channel of the chunk], zero beyond D
     const int l = threadIdx.x, c0 = blockIdx.y * CH;
-    const FeatureBlock b = feature_block<MODE>(n_tiles, tile_w, width, height, n_isects, empty, offsets, lt);
+    const WalkBlock b = walk_block<MODE>(xcd_remap(blockIdx.x, 4 * n_tiles, 4 * GSPL_XCD_RUN), tile_w);
+    const bool inside = (b.px < width) && (b.py < height);
+    int start = 0, end = 0;      // (`empty`: no list exists — N == 0 or no intersections — and `offsets` is not read)
+    if (!empty) block_list_range(lt, b.bx, b.by, width, height, n_isects, offsets, start, end);
 
     float T = 1.f;
     float acc[CH];
 #pragma unroll
     for (int c = 0; c < CH; ++c) acc[c] = 0.f;
-    int last = b.start;
-    bool done = !b.inside;
+    int last = start;
+    bool done = !inside;
 
     if (!__all(done)) {
-        int g_next = (b.start + l < b.end) ? flatten_ids[b.start + l] : 0;
-        for (int base = b.start; base < b.end; base += kRound) {
+        int g_next = (start + l < end) ? flatten_ids[start + l] : 0;
+        for (int base = start; base < end; base += kRound) {
             const int g = g_next;
-            if (base + kRound + l < b.end) g_next = flatten_ids[base + kRound + l];
-            const int ncand = compact_round(b, base, g, means2d, conics, opacities, s);
+            if (base + kRound + l < end) g_next = flatten_ids[base + kRound + l];
+            const RoundSlot r = compact_round(base + l < end, g, means2d, conics, opacities, b, s);
+            if (r.cand) { s_pos[r.slot] = base + l + 1; s_g[r.slot] = g; }
+            __builtin_amdgcn_wave_barrier();
+            const int ncand = r.ncand;
             if (ncand == 0) continue;
             // the candidates' feature rows: 64 lanes read consecutive channels of one row (two rows with CH == 32)
             for (int e = l; e < ncand * CH; e += 64) {
@@ -140,13 +79,9 @@ __global__ __launch_bounds__(64) void feature_fwd_kernel(
             __builtin_amdgcn_wave_barrier();
             bool all_done = false;
             for (int k = 0; k < ncand; ++k) {
-                float sigma;
-                const float alpha = candidate_alpha<MODE>(b, s, k, sigma);
-                const bool valid = !done && (sigma >= 0.f) && (alpha >= kAlphaMin);
-                const float next_T = T * (1.f - alpha);
-                const bool stop = valid && (TR::kStopInclusive ? (next_T <= kTStop) : (next_T < kTStop));
-                const bool contrib = valid && !stop;
-                const float wgt = contrib ? alpha * T : 0.f;
+                const PixelAlpha pa = pixel_alpha(s, k, b.pxf, b.pyf);
+                float wgt;
+                const bool contrib = blend_step<MODE>(pa.sigma, clamp_alpha<MODE>(pa.raw), T, done, wgt);
 #pragma unroll
                 for (int c = 0; c < CH; c += 4) {
                     const float4 f = *reinterpret_cast<const float4*>(&s_f[k * CH + c]);
@@ -155,16 +90,14 @@ __global__ __launch_bounds__(64) void feature_fwd_kernel(
                     acc[c + 2] = fmaf(f.z, wgt, acc[c + 2]);
                     acc[c + 3] = fmaf(f.w, wgt, acc[c + 3]);
                 }
-                T = contrib ? next_T : T;
                 last = contrib ? s_pos[k] : last;
-                done = done || stop;
                 if (__all(done)) { all_done = true; break; }
             }
             if (all_done) break;
         }
     }
 
-    if (b.inside) {
+    if (inside) {
         const int64_t pix = (int64_t)b.py * width + b.px, P = (int64_t)width * height;
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
@@ -192,19 +125,23 @@ __global__ __launch_bounds__(64) void feature_bwd_kernel(
     const float* __restrict__ v_out, float* __restrict__ v_features, ListTiles lt) {
     constexpr int LC = HALF ? 32 : 64;        // channels per workgroup
     constexpr int PXL = HALF ? 32 : 64;       // pixels per lane in phase 2
-    GSPL_FEATURE_LISTS();
+    __shared__ RoundLists s;
+    __shared__ int s_pos[kRound], s_g[kRound];      // list index + 1 and splat of each candidate
     __shared__ __attribute__((aligned(16))) float s_w[64 * kVStride];
     const int l = threadIdx.x, c0 = blockIdx.y * LC;
-    FeatureBlock b = feature_block<MODE>(n_tiles, tile_w, width, height, n_isects, false, offsets, lt);
+    const WalkBlock b = walk_block<MODE>(xcd_remap(blockIdx.x, 4 * n_tiles, 4 * GSPL_XCD_RUN), tile_w);
+    const bool inside = (b.px < width) && (b.py < height);
+    int start, end;
+    block_list_range(lt, b.bx, b.by, width, height, n_isects, offsets, start, end);
 
     // this pixel's walk ends behind its last contributing entry; the wave's behind the latest of them
     const int64_t P = (int64_t)width * height;
-    const int last = b.inside ? last_ids[(int64_t)b.py * width + b.px] : 0;
+    const int last = inside ? last_ids[(int64_t)b.py * width + b.px] : 0;
     int wave_last = last;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) wave_last = max(wave_last, __shfl_xor(wave_last, off));
-    b.end = min(b.end, wave_last);
-    if (b.end <= b.start) return;
+    end = min(end, wave_last);
+    if (end <= start) return;
 
     // phase 2's registers: v[j] = v_out[pixel p0 + j of the block, channel cl]; zero outside the image and beyond D
     const int cl = c0 + (l % LC), p0 = HALF ? (l >> 5) * 32 : 0;
@@ -213,7 +150,7 @@ __global__ __launch_bounds__(64) void feature_bwd_kernel(
     if (CHW) {
         // planes: read with lane = pixel (rows of eight pixels), turn through LDS
         for (int c = 0; c < LC; ++c)
-            s_w[c * kVStride + l] = (b.inside && c0 + c < D) ? v_out[(int64_t)(c0 + c) * P + (int64_t)b.py * width + b.px] : 0.f;
+            s_w[c * kVStride + l] = (inside && c0 + c < D) ? v_out[(int64_t)(c0 + c) * P + (int64_t)b.py * width + b.px] : 0.f;
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int j = 0; j < PXL; ++j) v[j] = s_w[(l % LC) * kVStride + p0 + j];
@@ -227,19 +164,22 @@ __global__ __launch_bounds__(64) void feature_bwd_kernel(
     }
 
     float T = 1.f;
-    int g_next = (b.start + l < b.end) ? flatten_ids[b.start + l] : 0;
-    for (int base = b.start; base < b.end; base += kRound) {
+    int g_next = (start + l < end) ? flatten_ids[start + l] : 0;
+    for (int base = start; base < end; base += kRound) {
         const int g = g_next;
-        if (base + kRound + l < b.end) g_next = flatten_ids[base + kRound + l];
-        const int ncand = compact_round(b, base, g, means2d, conics, opacities, s);
+        if (base + kRound + l < end) g_next = flatten_ids[base + kRound + l];
+        const RoundSlot r = compact_round(base + l < end, g, means2d, conics, opacities, b, s);
+        if (r.cand) { s_pos[r.slot] = base + l + 1; s_g[r.slot] = g; }
+        __builtin_amdgcn_wave_barrier();
+        const int ncand = r.ncand;
         if (ncand == 0) continue;
         // phase 1, lane = pixel: the weights of the round; bit k of `hit` = some pixel blended candidate k
         unsigned long long hit = 0ull;
         for (int k = 0; k < ncand; ++k) {
-            float sigma;
-            const float alpha = candidate_alpha<MODE>(b, s, k, sigma);
+            const PixelAlpha pa = pixel_alpha(s, k, b.pxf, b.pyf);
+            const float alpha = clamp_alpha<MODE>(pa.raw);
             // every entry in front of `last` that passed the forward's test was blended there (the stop comes behind `last`)
-            const bool contrib = (s_pos[k] <= last) && (sigma >= 0.f) && (alpha >= kAlphaMin);
+            const bool contrib = alpha_test(s_pos[k] <= last, pa.sigma, alpha);
             s_w[k * kWStride + l] = contrib ? alpha * T : 0.f;
             T = contrib ? T * (1.f - alpha) : T;
             hit |= (__ballot(contrib) != 0ull ? 1ull : 0ull) << k;
@@ -290,15 +230,15 @@ extern "C" int gspl_feature_fwd(int N, int64_t n_isects, int D, int mode, int la
     const bool empty = N == 0 || n_isects == 0;
     if (!empty && (!means2d || !conics || !features || !opacities || !offsets || !flatten_ids)) return fail_arg("feature_fwd: NULL required pointer");
     const ListTiles lt = list_tiles(grid);
-    const int ctw = (width + TILE - 1) / TILE, n_tiles = ctw * ((height + TILE - 1) / TILE);
+    const ComputeTiles ct = compute_tiles(image);
     hipStream_t s = (hipStream_t)stream;
     auto launch = [&](auto ch, auto inria, auto chw) {
         constexpr int CH = decltype(ch)::value;
         constexpr int MODE = decltype(inria)::value ? GSPL_MODE_INRIA : GSPL_MODE_GSPLAT;
         const int chunks = (D + CH - 1) / CH;
         if (chunks > 65535) return fail_arg("feature_fwd: D too large");
-        hipLaunchKernelGGL((feature_fwd_kernel<CH, MODE, decltype(chw)::value>), dim3(4 * n_tiles, chunks), dim3(64), 0, s,
-                           n_tiles, ctw, width, height, n_isects, D, empty, means2d, conics, features, opacities, backgrounds, offsets, flatten_ids,
+        hipLaunchKernelGGL((feature_fwd_kernel<CH, MODE, decltype(chw)::value>), dim3(4 * ct.n, chunks), dim3(64), 0, s,
+                           ct.n, ct.w, width, height, n_isects, D, empty, means2d, conics, features, opacities, backgrounds, offsets, flatten_ids,
                            out, out_alphas, final_Ts, last_ids, lt);
         return check_launch("feature_fwd");
     };
@@ -321,15 +261,15 @@ extern "C" int gspl_feature_bwd(int N, int64_t n_isects, int D, int mode, int la
     if (N == 0 || n_isects == 0) return GSPL_OK;      // nothing was blended: v_features stays as the caller zeroed it
     if (!means2d || !conics || !opacities || !offsets || !flatten_ids || !last_ids || !v_out || !v_features) return fail_arg("feature_bwd: NULL required pointer");
     const ListTiles lt = list_tiles(grid);
-    const int ctw = (width + TILE - 1) / TILE, n_tiles = ctw * ((height + TILE - 1) / TILE);
+    const ComputeTiles ct = compute_tiles(image);
     const bool half = D <= 32;
     const int chunks = half ? 1 : (D + 63) / 64;
     if (chunks > 65535) return fail_arg("feature_bwd: D too large");
     hipStream_t s = (hipStream_t)stream;
     return dispatch_bools([&](auto inria, auto chw, auto hf) {
         constexpr int MODE = decltype(inria)::value ? GSPL_MODE_INRIA : GSPL_MODE_GSPLAT;
-        hipLaunchKernelGGL((feature_bwd_kernel<MODE, decltype(chw)::value, decltype(hf)::value>), dim3(4 * n_tiles, chunks), dim3(64), 0, s,
-                           n_tiles, ctw, width, height, n_isects, D, means2d, conics, opacities, offsets, flatten_ids, last_ids, v_out, v_features, lt);
+        hipLaunchKernelGGL((feature_bwd_kernel<MODE, decltype(chw)::value, decltype(hf)::value>), dim3(4 * ct.n, chunks), dim3(64), 0, s,
+                           ct.n, ct.w, width, height, n_isects, D, means2d, conics, opacities, offsets, flatten_ids, last_ids, v_out, v_features, lt);
         return check_launch("feature_bwd");
     }, mode != GSPL_MODE_GSPLAT, layout != GSPL_LAYOUT_HWC, half);
 }

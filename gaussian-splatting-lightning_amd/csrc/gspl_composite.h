@@ -1,5 +1,5 @@
 // gspl_composite.h — device helpers shared by the compositing kernels (composite.hip: forward + per-splat statistics;
-// composite_bwd.hip: backward).  gfx950, wave64.
+// composite_bwd.hip: backward; features.hip: wide features), among them the one definition of the 8x8 block walk.  gfx950, wave64.
 //
 // The compositing rule restated here is the published 3DGS rule with the per-API constants of SURVEY.md Appendix B (ModeTraits
 // in gspl_device.h); call sites replaced: internal/renderers/gsplat_v1_renderer.py:588-601 (`rasterize_to_pixels`),
@@ -197,12 +197,115 @@ static inline ListTiles list_tiles(TileGrid grid) {
     lt.n = grid.n();
     return lt;
 }
+// ... and the 16x16 compute grid of an image: what the kernels' `tile_w` and `n_tiles` are, whatever the lists were cut on
+struct ImageSize { int width, height; };
+struct ComputeTiles { int w, n; };
+static inline ComputeTiles compute_tiles(ImageSize image) {
+    const int w = (image.width + TILE - 1) / TILE;
+    return ComputeTiles{w, w * ((image.height + TILE - 1) / TILE)};
+}
 __device__ __forceinline__ void block_list_range(const ListTiles& lt, int bx, int by, int width, int height, int64_t n_isects,
                                                  const int32_t* __restrict__ offsets, int& start, int& end) {
     if (bx * 8 >= width || by * 8 >= height) { start = end = 0; return; }      // (a block of the compute grid outside the image)
     const int t = (by >> (lt.log2 - 3)) * lt.w + (bx >> (lt.log2 - 3));
     start = offsets[t];
     end = (t + 1 < lt.n || n_isects < 0) ? offsets[t + 1] : (int)n_isects;
+}
+
+// ---- the 8x8 block walk -----------------------------------------------------------------------------------------------------------
+// One wave per 8x8 pixel block, one pixel per lane, the block's list in rounds of 64 entries: composite_fwd_kernel and
+// composite_scores_kernel (composite.hip), composite_bwd_block_kernel (composite_bwd.hip), feature_fwd_kernel and feature_bwd_kernel
+// (features.hip).  The kernels must take the same discrete decisions bit for bit (the hit flags equal `count > 0` of the statistics
+// pass, the wide-feature image equals the narrow kernels', a backward re-derives the pairs its forward blended), so the block, the
+// round, the per-pixel alpha and the blending decision are defined here once.  What a kernel keeps to itself: where its list comes
+// from (block_list_range or tile_range) and in which direction it walks it, what it stages per candidate beside the six common
+// arrays, and what it does with a blended pair.  composite_bwd2_kernel (two pixels per lane, band_half_mask) has its own packed walk.
+struct WalkBlock {
+    int bx, by, w;                    // the block in units of 8 pixels; w: its quadrant of the 16x16 compute tile
+    int px, py;                       // this lane's pixel
+    float pxf, pyf;                   // ... and its centre
+    float qx0, qx1, qy0, qy1;         // the block's pixel-centre bounds (wave-uniform)
+};
+// unit = 4 * compute tile + quadrant; tile_w: compute tiles per row
+template <int MODE>
+__device__ __forceinline__ WalkBlock walk_block(int unit, int tile_w) {
+    using TR = ModeTraits<MODE>;
+    WalkBlock b;
+    const int tile = unit >> 2, l = threadIdx.x;
+    b.w = unit & 3;
+    b.bx = (tile % tile_w) * 2 + (b.w & 1); b.by = (tile / tile_w) * 2 + (b.w >> 1);
+    b.px = b.bx * 8 + (l & 7); b.py = b.by * 8 + (l >> 3);
+    b.pxf = (float)b.px + TR::kPixelCentre; b.pyf = (float)b.py + TR::kPixelCentre;
+    b.qx0 = (float)(b.bx * 8) + TR::kPixelCentre; b.qx1 = b.qx0 + 7.f;
+    b.qy0 = (float)(b.by * 8) + TR::kPixelCentre; b.qy1 = b.qy0 + 7.f;
+    return b;
+}
+
+// One round's candidates in LDS, structure of arrays: centre, sigma_coef, opacity.  `__shared__ RoundLists s;`
+struct RoundLists { float x[64], y[64], ha[64], k[64], hd[64], op[64]; };
+struct RoundSlot {
+    int ncand;        // candidates of the round (wave-uniform)
+    int slot;         // this lane's candidate goes to slot `slot`, if `cand`: the number of candidates in lower lanes, so the slots
+    bool cand;        // follow the lanes' order whichever way the caller walks its list
+    float b, c;       // the conic's b and c as this lane loaded them
+};
+// Lane l holds one list entry (`has`: there is one; g: its splat), tests it against the block and the survivors' common fields land in
+// slots 0 .. ncand - 1.  The caller stages what else it needs at r.slot and then closes the round with a barrier of its own: a wave
+// barrier, or __syncthreads() in a one-wave workgroup.  (composite_fwd_kernel keeps its own copy of this: its arrays carry a padding
+// entry for the packed loop, its colours are staged with the gather, and it runs without wave barriers.  Built on this helper — arrays
+// of 66, no barrier — its D = 3 instantiations go from 42 / 56 to 43 / 58 VGPRs: profiles/block_walk_kernel_resources.txt.)
+__device__ __forceinline__ RoundSlot compact_round(bool has, int g, const float* __restrict__ means2d, const float* __restrict__ conics,
+                                                   const float* __restrict__ opacities, const WalkBlock& b, RoundLists& s) {
+    RoundSlot r;
+    r.cand = false;
+    float mx = 0.f, my = 0.f, ca = 0.f, op = 0.f;
+    r.b = r.c = 0.f;
+    if (has) {
+        ca = conics[g * 3 + 0]; r.b = conics[g * 3 + 1]; r.c = conics[g * 3 + 2]; op = opacities[g];
+        mx = means2d[g * 2 + 0]; my = means2d[g * 2 + 1];
+        r.cand = box_reachable(mx, my, ca, r.b, r.c, op, b.qx0, b.qx1, b.qy0, b.qy1);
+    }
+    const unsigned long long mask = __ballot(r.cand);
+    r.ncand = __builtin_popcountll(mask);
+    r.slot = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+    __builtin_amdgcn_wave_barrier();
+    if (r.cand) {
+        const SigmaCoef sc = sigma_coef(ca, r.b, r.c);
+        s.x[r.slot] = mx; s.y[r.slot] = my; s.ha[r.slot] = sc.ha; s.k[r.slot] = sc.k; s.hd[r.slot] = sc.hd; s.op[r.slot] = op;
+    }
+    return r;
+}
+
+// Candidate k at the pixel centre (pxf, pyf): sigma and the unclamped opacity * exp(-sigma).  Each component of the packed loops of
+// composite_fwd_kernel and composite_bwd2_kernel (eval_sigma2, exp2 of sigma * -log2 e) is this expression tree.
+struct PixelAlpha { float dx, dy, sigma, raw; };
+__device__ __forceinline__ PixelAlpha pixel_alpha(const RoundLists& s, int k, float pxf, float pyf) {
+    PixelAlpha a;
+    a.dx = s.x[k] - pxf; a.dy = s.y[k] - pyf;
+    a.sigma = eval_sigma(s.ha[k], s.k[k], s.hd[k], a.dx, a.dy);
+    a.raw = s.op[k] * __builtin_amdgcn_exp2f(a.sigma * -1.4426950408889634f);
+    return a;
+}
+template <int MODE>
+__device__ __forceinline__ float clamp_alpha(float raw) { return fminf(ModeTraits<MODE>::kAlphaMax, raw); }
+
+// "this pixel takes this splat" (alpha clamped or not: kAlphaMax > 1/255).  `live`: the forward's "not done", a backward's "not behind
+// the pixel's last contributor" — an operand here and not `live && alpha_test(..)` at the callers: that associates the three conditions
+// the other way round, and hipcc then schedules composite_fwd_kernel's inner loop differently (profiles/block_walk_ab.txt).
+__device__ __forceinline__ bool alpha_test(bool live, float sigma, float alpha) { return live && (sigma >= 0.f) && (alpha >= kAlphaMin); }
+
+// The forward's blending decision for one (pixel, candidate): returns whether the pair is blended, `wgt` = its weight alpha T (0 if
+// not), and moves T and `done` on.  A pixel stops IN FRONT of the splat that would take its transmittance below 1e-4.
+template <int MODE>
+__device__ __forceinline__ bool blend_step(float sigma, float alpha, float& T, bool& done, float& wgt) {
+    const bool valid = alpha_test(!done, sigma, alpha);
+    const float next_T = T * (1.f - alpha);
+    const bool stop = valid && (ModeTraits<MODE>::kStopInclusive ? (next_T <= kTStop) : (next_T < kTStop));
+    const bool contrib = valid && !stop;
+    wgt = contrib ? alpha * T : 0.f;
+    T = contrib ? next_T : T;
+    done = done || stop;
+    return contrib;
 }
 
 // A table of float arrays to clear, and the grid that clears it: `blocks` workgroups of NT threads each, workgroup `block` of them.
@@ -235,10 +338,9 @@ __device__ __forceinline__ void zero_fill_body(const FillJob& job, unsigned bloc
 // number of per-splat gradient values accumulated per (tile, splat): xy(2) conic(3) opacity(1) colour(D) [+abs xy(2)]
 template <int D, bool ABS> struct BwdVals { static constexpr int N = 6 + D + (ABS ? 2 : 0); };
 
-// argument groups of the compositing calls below the ABI (gspl_host.h has the tile grid): the splats as compositing reads them, the
-// image, and the per-tile lists (n_isects < 0: `offsets` has one more entry, the list length, left there by the device)
+// argument groups of the compositing calls below the ABI (gspl_host.h has the tile grid; ImageSize: above): the splats as compositing
+// reads them, and the per-tile lists (n_isects < 0: `offsets` has one more entry, the list length, left there by the device)
 struct CompositeSplats { const float* means2d; const float* conics; const float* colors; const float* opacities; const float* backgrounds; };
-struct ImageSize { int width, height; };
 struct TileLists { const int32_t* offsets; const int32_t* flatten_ids; int64_t n_isects; };
 
 int check_composite_args(int N, int64_t n_isects, int D, int mode, int layout, ImageSize image, TileGrid grid, const char* who);

@@ -185,9 +185,8 @@ __device__ __forceinline__ bool surfel_hit(const float* r, float x, float y, Sur
 }
 
 __device__ __forceinline__ void surfel_range(int tile, int n_tiles, int64_t n_isects, const int32_t* __restrict__ offsets, int& start, int& end) {
-    if (n_isects <= 0) { start = end = 0; return; }
-    start = offsets[tile];
-    end = tile + 1 < n_tiles ? offsets[tile + 1] : (int)n_isects;
+    if (n_isects <= 0) { start = end = 0; return; }      // (no list: `offsets` is not read)
+    tile_range(tile, n_tiles, n_isects, offsets, start, end);
 }
 
 // stage the record of list entry `idx` into s (18 floats)

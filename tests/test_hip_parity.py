@@ -7,6 +7,7 @@ Integer / index outputs (radii, tile counts, sort keys, offsets) are compared bi
 Pixels / splats whose discrete skip-stop-clamp decision sits within 2e-5 relative of its threshold
 ("fragile", flagged by the fp64 oracle) are excluded from the strict bound and must be rare.
 """
+import functools
 import os
 
 import numpy as np
@@ -691,6 +692,60 @@ def test_composite_layout_chw_equals_hwc(hip):
     o1, a1, _, l1 = hip_composite_fwd(O.MODE_INRIA, *args, layout=L.GSPL_LAYOUT_HWC)
     o2, a2, _, l2 = hip_composite_fwd(O.MODE_INRIA, *args, layout=L.GSPL_LAYOUT_CHW)
     assert torch.equal(o1.permute(2, 0, 1), o2) and torch.equal(a1, a2) and torch.equal(l1, l2)
+
+
+@functools.lru_cache(maxsize=None)
+def _block_walk_case(mode, tile):
+    """37 x 21 pixels: a 3 x 2 compute grid whose last column and row of 8x8 blocks lie outside the image and whose last blocks inside
+    it are partial on both axes; large opaque splats, so that lists run over several rounds of 64 entries (the longest: 233-263 /
+    393-421 / 583-600 with tile 8 / 16 / 32), ~95 of the 777 pixels stop early, half stay open and 308 opacities sit at the clamp."""
+    W, H, n, D = 37, 21, 600, 8
+    means, scales, quats, opac, _ = O.synthetic_scene(n, seed=11)
+    cam = O.synthetic_camera(W, H, 40.0)
+    res = O.project_gaussians(means, scales * 6.0, 1.0, quats, cam["world_to_camera"], cam["fx"], cam["fy"], cam["cx"], cam["cy"], H, W)
+    xys, depths, radii, conics, comp = res[0], res[1], res[2], res[3], res[4]
+    op = torch.clamp(opac.reshape(-1) * comp * 4.0, max=1.0).float()
+    if mode == O.MODE_INRIA:
+        xys = xys - 0.5
+    _, _, flat, offs = O.isect_tiles(mode, xys, radii, depths, W, H, block=tile)
+    g = torch.Generator().manual_seed(11)
+    colors, bg = torch.rand(n, D, generator=g), torch.rand(D, generator=g)
+    v_out, v_alpha = torch.randn(H, W, D, generator=g), torch.randn(H, W, generator=g)
+    longest = int(np.diff(np.append(offs, len(flat))).max())
+    return W, H, xys.float(), conics.float(), colors, op, bg, torch.as_tensor(flat), torch.as_tensor(offs), v_out, v_alpha, longest
+
+
+@pytest.mark.parametrize("mode", [O.MODE_GSPLAT, O.MODE_INRIA])
+@pytest.mark.parametrize("tile", [8, 16, 32])
+def test_block_walk_kernels_take_the_same_decisions(hip, mode, tile):
+    """The five kernels that walk a list with one wave per 8x8 block share one definition of the walk (gspl_composite.h); what rests on
+    it, GPU against GPU and bit for bit: the forward's hit flags are the statistics pass's `count > 0`, the backward (the 16-pixel
+    kernel with tile 16, the block kernel otherwise) re-derives exactly the pairs the forward blended, and the wide-feature forward
+    gives the narrow forward's image, alpha, transmittance and last index in both layouts."""
+    from gspl_amd import _lib as L
+    from gspl_amd import ops
+    W, H, xys, conics, colors, op, bg, flat, offs, v_out, v_alpha, longest = _block_walk_case(mode, tile)
+    assert longest > 3 * 64 and (op == 1.0).sum() > 100
+    c = lambda a: a.contiguous().to(_dev())
+    dxy, dcon, dcol, dop, dbg, dflat, doffs = c(xys), c(conics), c(colors), c(op), c(bg), c(flat), c(offs)
+    n, D = colors.shape
+    hits = torch.zeros(n, dtype=torch.uint8, device=_dev())
+    out, alphas, final_T, last = hip_composite_fwd(mode, dxy, dcon, dcol, dop, dbg, W, H, doffs, dflat, hits=hits, tile=tile)
+    assert 0 < int(hits.sum()) < n
+    if tile == 16:
+        count = ops.composite_scores(dxy, dcon, dop, W, H, 16, doffs, dflat, mode=mode)[0]
+        assert torch.equal(hits != 0, count > 0)
+    got = hip_composite_bwd(mode, dxy, dcon, dcol, dop, dbg, W, H, doffs, dflat, final_T, last, c(v_out), c(v_alpha), tile=tile)
+    assert torch.equal(got["hit"], hits)
+    for layout in (L.GSPL_LAYOUT_HWC, L.GSPL_LAYOUT_CHW):
+        narrow = (out, alphas, final_T, last) if layout == L.GSPL_LAYOUT_HWC else \
+            hip_composite_fwd(mode, dxy, dcon, dcol, dop, dbg, W, H, doffs, dflat, layout=layout, tile=tile)
+        wide = (torch.empty_like(narrow[0]), torch.empty_like(alphas), torch.empty_like(final_T), torch.empty_like(last))
+        L.check(L.lib().gspl_feature_fwd(n, dflat.shape[0], D, mode, layout, L.ptr(dxy), L.ptr(dcon), L.ptr(dcol), L.ptr(dop), L.ptr(dbg),
+                                         W, H, tile, (W + tile - 1) // tile, (H + tile - 1) // tile, L.ptr(doffs), L.ptr(dflat),
+                                         L.ptr(wide[0]), L.ptr(wide[1]), L.ptr(wide[2]), L.ptr(wide[3]), L.stream()), "gspl_feature_fwd")
+        for a, b, name in zip(wide, narrow, ("image", "alphas", "final_Ts", "last_ids")):
+            assert torch.equal(a, b), f"{name} layout={layout}"
 
 
 def test_composite_no_intersections_gives_background(hip):
