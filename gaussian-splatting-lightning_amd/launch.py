@@ -11,6 +11,10 @@ It also lets `torch.optim.lr_scheduler.LambdaLR` take the `verbose=` keyword tha
 `verbose=False` (internal/output_processors/bilagrid.py and exposure.py, the appearance-embedding, deformable, SWAG and RGB-MLP
 renderers).  Only in this launched process, and only when the installed torch rejects the keyword; importing the package patches
 nothing in torch.
+
+With `GSPL_HIP_GS4D=1` in the environment the viewer's `--vanilla_gs4d` route is served by the HIP plugin: the launcher binds
+`internal.renderers.vanilla_gs4d_renderer.VanillaGS4DRenderer` (which internal/viewer/viewer.py imports when it builds that renderer)
+to `gspl_amd.renderers.HipVanillaGS4DRenderer`, in this launched process only.  Without the variable nothing is bound.
 """
 import inspect
 import os
@@ -45,6 +49,17 @@ def accept_lambdalr_verbose() -> bool:
     return True
 
 
+def bind_gs4d_renderer() -> bool:
+    """With GSPL_HIP_GS4D=1: `internal.renderers.vanilla_gs4d_renderer.VanillaGS4DRenderer` becomes the HIP plugin (same constructor,
+    same model directory); returns whether it did.  The script's directory must be on sys.path already."""
+    if os.environ.get("GSPL_HIP_GS4D", "0") != "1":
+        return False
+    import importlib
+    from .renderers import HipVanillaGS4DRenderer
+    importlib.import_module("internal.renderers.vanilla_gs4d_renderer").VanillaGS4DRenderer = HipVanillaGS4DRenderer
+    return True
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     if not argv:
@@ -55,6 +70,7 @@ def main(argv=None):
     script = argv[0]
     sys.argv = argv
     sys.path.insert(0, os.path.dirname(os.path.abspath(script)))      # what `python <script>` puts first
+    bind_gs4d_renderer()
     runpy.run_path(script, run_name="__main__")
 
 

@@ -32,6 +32,8 @@ reference's renderers call (same names, argument meaning and error behaviour):
       hashgrid_levels, HashGridLevels, hashgrid_table, hashgrid_encode, hashgrid_forward, hashgrid_backward
   The appearance-embedding route's per-Gaussian MLP (internal/renderers/gsplat_appearance_embedding_renderer.py:50-93, `tcnn: false`)
       appearance_mlp, appearance_mlp_check, appearance_mlp_forward, appearance_mlp_backward
+  The 4D-GS route's HexPlane / K-Planes field (internal/model_components/gs4d_hexplane.py: six `F.grid_sample` per level and a product)
+      hexplane_layout, HexPlaneLayout, hexplane_pack, hexplane_box, hexplane_encode, hexplane_forward, hexplane_backward
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -68,6 +70,7 @@ from .mesh import tsdf_init, tsdf_table, tsdf_fuse, marching_tetrahedra, marchin
 from .knn import knn_points, knn_graph, KnnGraph, smooth_features, _SmoothFn
 from .hashgrid import hashgrid_levels, HashGridLevels, hashgrid_table, hashgrid_encode, hashgrid_forward, hashgrid_backward, _HashGridFn
 from .appearance import appearance_mlp, appearance_mlp_check, appearance_mlp_forward, appearance_mlp_backward, _AppearanceMlpFn
+from .hexplane import hexplane_layout, HexPlaneLayout, hexplane_pack, hexplane_box, hexplane_encode, hexplane_forward, hexplane_backward, _HexPlaneFn
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

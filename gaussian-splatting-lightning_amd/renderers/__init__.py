@@ -23,3 +23,4 @@ from .hip_gsplat_contrastive_feature_renderer import HipGSplatContrastiveFeature
 from .hip_pvg_renderer import HipPeriodicVibrationGaussianRenderer, HipPeriodicVibrationGaussianRendererModule  # noqa: F401,E402
 from .hip_swag_renderer import HipSWAGRenderer  # noqa: F401,E402
 from .hip_gsplat_appearance_embedding_renderer import HipGSplatAppearanceEmbeddingRenderer, HipGSplatAppearanceEmbeddingRendererModule  # noqa: F401,E402
+from .hip_vanilla_gs4d_renderer import HipVanillaGS4DRenderer  # noqa: F401,E402

@@ -1161,6 +1161,41 @@ int gspl_appearance_mlp_bwd(int N, int F, int E, int H, int n_layers, int n_out,
                             const float* const* weights, const float* const* biases, const float* v_out, float* v_features,
                             float* v_params, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 22. The HexPlane / K-Planes field of the 4D-GS route (csrc/hexplane.hip).  PURELY ADDITIVE: two new entry points, no new struct,
+ *    nothing existing changes, GSPL_ABI_VERSION stays 39.  What `HexPlaneField.forward` of
+ *    internal/model_components/gs4d_hexplane.py computes with six `F.grid_sample` calls per level (bilinear, align_corners=True,
+ *    padding_mode='border'), a product chain and a cat.  The reference's arithmetic is torch code, so it is pinned directly
+ *    (tests/hexplane_oracle.py against tests/golden/ref_hexplane.npz).
+ *
+ *  x [N,3] f32; t [N] f32 per point, or NULL and ONE value `t_uniform` for the call; F = 8, 16, 32 or 64 features; L = 1 .. 8 levels.
+ *  HOST arrays (`ops.hexplane_layout`):
+ *      resolutions [L,4]  R_x, R_y, R_z, R_t of each level (the level's multiplier applies to the three spatial axes only), 1 .. 32768
+ *      offsets [6 L + 1]  first row of plane p of level l at [6 l + p]; offsets[6 L] = rows of the table < 2^31
+ *      box [6]            aabb[0] (the reference keeps the MAXIMUM corner there), then float32(2 / (aabb[1] - aabb[0]))
+ *  The six planes of a level are the pairs (a, b) of itertools.combinations(range(4), 2): xy, xz, xt, yz, yt, zt.  Plane (a, b) has
+ *  R_a R_b rows of F floats, CHANNEL-LAST, row = i_b R_a + i_a (the reference's parameter [1, F, R_b, R_a] with the channels moved
+ *  last: a corner is one contiguous row).  offsets must give every plane exactly R_a R_b rows.
+ *  Per point:  p = ((x - aabb[0]) scale - 1 per axis, t): the time is used as it comes.  Per axis of a level, in float32, each
+ *  operation rounded once and none contracted:
+ *      i = ((c + 1) / 2) (R - 1), clamped to [0, R - 1];  i0 = floor(i);  weights (1 - f, f) with f = i - i0
+ *  A corner with index R (only when i == R - 1) contributes nothing.
+ *      out[n, l F + f] = product over the six planes of (sum over the four corners of weight table[row, f])
+ *
+ *  gspl_hexplane_fwd: out [N, L F].  One launch, one level per blockIdx.y.
+ *  gspl_hexplane_bwd: v_out [N, L F].  v_table (nullable), the table's shape, is ACCUMULATED into (the caller clears it) with fp32
+ *    atomics, one float per lane and whole rows per wave-instruction: the sum depends on arrival order in the last bits.  A
+ *    (point, level) whose F values of v_out are all zero adds nothing and is skipped before it reads x or the table.
+ *    v_x (nullable) [N,3] is WRITTEN, without atomics; an axis whose unclamped i is not strictly inside (0, R - 1) gets no gradient
+ *    from that level, as grid_sample's border padding has it.  There is no gradient for t.
+ *  table, out and v_out must be aligned to 16 bytes.  N == 0: no launch.
+ * ---------------------------------------------------------------------------------------- */
+int gspl_hexplane_fwd(int N, int F, int L, const uint32_t* resolutions, const uint32_t* offsets, const float* box,
+                      const float* x, const float* t, float t_uniform, const float* table, float* out, void* stream);
+int gspl_hexplane_bwd(int N, int F, int L, const uint32_t* resolutions, const uint32_t* offsets, const float* box,
+                      const float* x, const float* t, float t_uniform, const float* table, const float* v_out,
+                      float* v_table, float* v_x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
