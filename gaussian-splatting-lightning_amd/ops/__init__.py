@@ -34,6 +34,10 @@ reference's renderers call (same names, argument meaning and error behaviour):
       appearance_mlp, appearance_mlp_check, appearance_mlp_forward, appearance_mlp_backward
   The 4D-GS route's HexPlane / K-Planes field (internal/model_components/gs4d_hexplane.py: six `F.grid_sample` per level and a product)
       hexplane_layout, HexPlaneLayout, hexplane_pack, hexplane_box, hexplane_encode, hexplane_forward, hexplane_backward
+  The SpotLessSplats route (internal/metrics/spotless_metrics.py: the mask MLP behind a bilinear resampling, `robust_mask`, the error
+  histogram of `update_running_stats`, the masked L1; the module-level API is gspl_amd.spotless)
+      spotless_mask, spotless_error_stats, spotless_masked_l1, and the launches alone: spotless_mask_forward / _backward,
+      spotless_masked_l1_forward / _backward
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -71,6 +75,8 @@ from .knn import knn_points, knn_graph, KnnGraph, smooth_features, _SmoothFn
 from .hashgrid import hashgrid_levels, HashGridLevels, hashgrid_table, hashgrid_encode, hashgrid_forward, hashgrid_backward, _HashGridFn
 from .appearance import appearance_mlp, appearance_mlp_check, appearance_mlp_forward, appearance_mlp_backward, _AppearanceMlpFn
 from .hexplane import hexplane_layout, HexPlaneLayout, hexplane_pack, hexplane_box, hexplane_encode, hexplane_forward, hexplane_backward, _HexPlaneFn
+from .spotless import (spotless_mask, spotless_mask_forward, spotless_mask_backward, spotless_error_stats, spotless_masked_l1,
+                       spotless_masked_l1_forward, spotless_masked_l1_backward, _SpotlessMaskFn, _MaskedL1Fn)
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

@@ -1196,6 +1196,61 @@ int gspl_hexplane_bwd(int N, int F, int L, const uint32_t* resolutions, const ui
                       const float* x, const float* t, float t_uniform, const float* table, const float* v_out,
                       float* v_table, float* v_x, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 23. The SpotLessSplats route outside the rasterizer (csrc/spotless.hip).  PURELY ADDITIVE: seven new entry points, no new struct,
+ *    nothing existing changes, GSPL_ABI_VERSION stays 39.  What `SpotLessMetricsModule` of internal/metrics/spotless_metrics.py
+ *    computes in `mlp_mask`, `robust_mask`, `update_running_stats` (its histogram) and its masked L1.  The reference's arithmetic is
+ *    torch code, so it is pinned directly (tests/spotless_oracle.py against tests/golden/ref_spotless.npz).  fp32, device pointers only,
+ *    no float atomics: every float sum is taken in a fixed order, the same bits on every run.
+ *
+ *  The mask predictor.  The first linear layer is folded through the bilinear resampling by the caller (gspl_amd.spotless):
+ *      G [h0, w0, 16] channel-last = W1[:, :C] sf at the feature map's own resolution;  A [mh, 16] = pe_y W1[:, C:C+40]^T + b1;
+ *      B [mw, 16] = pe_x W1[:, C+40:]^T;  w2 [16], b2 [1] the second layer.  16 hidden units only.
+ *      z[i, j, :] = bilinear(G)[i, j, :] + A[i, :] + B[j, :];   mask[i, j] = sigmoid(b2 + sum_c w2[c] relu(z[i, j, c]))
+ *  H == W == 0: out [mh, mw] is the mask.  Otherwise out [H, W] is the mask resampled bilinearly once more, the network evaluated at
+ *  the four source pixels of every output pixel; the mask itself is not written.
+ *  Both resamplings follow F.interpolate(mode="bilinear", align_corners=False), no antialiasing; per axis, in float32:
+ *      src = max(fma(I / O, o + 0.5, -0.5), 0);  i0 = floor(src);  i1 = min(i0 + 1, I - 1);  weights (1 - l, l) with l = src - i0
+ *  The product and the sum of src are ONE fused operation, as torch's CPU and GPU kernels have it (their weights, read out with
+ *  one-hot inputs, equal this rule's bit for bit and differ from the unfused one); every other operation is rounded on its own.
+ *  and a sample is  (1 - ly) ((1 - lx) v00 + lx v01) + ly ((1 - lx) v10 + lx v11).
+ *  Every dimension is 2 .. 16384 (the reference's positional encoding divides by height - 1).  G, A, B and the workspace must be
+ *  aligned to 16 bytes.
+ *
+ *  gspl_spotless_mask_fwd: one launch.
+ *  gspl_spotless_mask_bwd: v_out in the shape of out -> v_G, v_A, v_B in the shapes of G, A, B and v_w [17] (v_w2, then v_b2), every
+ *    element WRITTEN.  v = the adjoint of the second resampling of v_out (gathered, when there is one); dy = v s (1 - s);
+ *    dz = dy w2 [z > 0]; v_A the row sums of dz, v_B its column sums, v_G its adjoint bilinear, v_w2 = sum dy relu(z), v_b2 = sum dy.
+ *    Hidden activations are recomputed.  Two launches: one wave per (64 mask columns, row of G) leaves partial sums in `workspace`
+ *    (gspl_spotless_mask_workspace_bytes), the second adds them in index order.  A pixel with v == 0 is not evaluated.
+ *
+ *  gspl_spotless_error_stats: render, gt [3, H, W]; thresholds [2] (lower, upper) on the DEVICE; edges [bins + 1] on the device, the
+ *    float32 linspace(0, 1, bins + 1); 1 <= bins <= 15360.  One launch writes
+ *      err [H, W] = ((|d0| + |d1|) + |d2|) / 3 with a true division;
+ *      counts [bins] int32, ADDED to (the caller clears it): torch.histogram's rules over (0, 1) — bin k holds edges[k] <= v <
+ *        edges[k + 1], the last bin includes 1, values outside [0, 1] and NaN are dropped; integer atomics on a histogram in LDS;
+ *      lower_mask, upper_mask [H, W]: 1 where err < threshold (strictly) at the pixel, or at 5 or more of the 9 pixels of its
+ *        zero-padded 3 x 3 neighbourhood; else 0.
+ *
+ *  gspl_spotless_masked_l1_fwd: out [1] = sum_p mask[p] ((|d0| + |d1|) + |d2|) / (3 H W) by a fixed two-level sum; partials holds
+ *    gspl_spotless_l1_partials(H W) floats.
+ *  gspl_spotless_masked_l1_bwd: v_render [3, H, W] = sign(render - gt) grad_out[0] mask / (3 H W), rounded to float32 once, sign(0) = 0;
+ *    grad_out on the device.
+ * ---------------------------------------------------------------------------------------- */
+int gspl_spotless_mask_fwd(int h0, int w0, int mh, int mw, int H, int W, const float* G, const float* A, const float* B,
+                           const float* w2, const float* b2, float* out, void* stream);
+size_t gspl_spotless_mask_workspace_bytes(int h0, int w0, int mh, int mw);
+int gspl_spotless_mask_bwd(int h0, int w0, int mh, int mw, int H, int W, const float* G, const float* A, const float* B,
+                           const float* w2, const float* b2, const float* v_out, float* v_G, float* v_A, float* v_B, float* v_w,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int gspl_spotless_error_stats(int H, int W, int bins, const float* render, const float* gt, const float* thresholds, const float* edges,
+                              float* err, int32_t* counts, float* lower_mask, float* upper_mask, void* stream);
+int gspl_spotless_l1_partials(int64_t n);
+int gspl_spotless_masked_l1_fwd(int H, int W, const float* render, const float* gt, const float* mask, float* partials, float* out,
+                                void* stream);
+int gspl_spotless_masked_l1_bwd(int H, int W, const float* render, const float* gt, const float* mask, const float* grad_out,
+                                float* v_render, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
