@@ -22,6 +22,7 @@
 // torch's own kernels compute it (pinned against F.interpolate's weights in tests/test_spotless_cpu.py), nothing else contracted.
 #include <cstdint>
 #include "gspl_host.h"
+#include "gspl_resample.h"
 
 namespace gspl {
 namespace {
@@ -31,24 +32,7 @@ constexpr int SLS_BLOCK = 256;
 constexpr int SLS_MAX_DIM = 16384;     // every map, mask and image dimension: sls_range's float estimate is then off by far less than 1
 constexpr int SLS_MAX_BINS = 15360;    // 60 KB of LDS for the private histogram
 
-struct SlsAxis {
-    int i0, i1;
-    float l, h;      // weights of i1 and i0
-};
-
-// output index o of an axis resampled from I to O entries; scale = (float)I / (float)O
-__device__ __forceinline__ SlsAxis sls_axis(float scale, int o, int I) {
-#pragma clang fp contract(off)
-    const float centre = (float)o + 0.5f;
-    float src = fmaf(scale, centre, -0.5f);      // ONE rounding: torch's kernels, CPU and GPU, are compiled with this product and sum fused
-    src = src < 0.f ? 0.f : src;
-    SlsAxis a;
-    a.i0 = min((int)src, I - 1);
-    a.i1 = min(a.i0 + 1, I - 1);
-    a.l = fminf(fmaxf(src - (float)a.i0, 0.f), 1.f);
-    a.h = 1.f - a.l;
-    return a;
-}
+// SlsAxis and sls_axis (the rule of one resampled axis) are in gspl_resample.h, shared with segany.hip.
 
 // the weight with which output o reads source s
 __device__ __forceinline__ float sls_weight(const SlsAxis& a, int s) { return (a.i0 == s ? a.h : 0.f) + (a.i1 == s ? a.l : 0.f); }

@@ -38,6 +38,10 @@ reference's renderers call (same names, argument meaning and error behaviour):
   histogram of `update_running_stats`, the masked L1; the module-level API is gspl_amd.spotless)
       spotless_mask, spotless_error_stats, spotless_masked_l1, and the launches alone: spotless_mask_forward / _backward,
       spotless_masked_l1_forward / _backward
+  The SegAnyGS training step behind the renderer (internal/segany_splatting.py:152-260, 317-419: `mask_preprocess` and the loss of
+  `forward_with_loss_calculation`; the module-level API is gspl_amd.segany.use_hip_loss)
+      segany_mask_stats, segany_pack_membership, segany_pair_labels, segany_correspondence_loss, and the launches alone:
+      segany_loss_forward / segany_loss_backward
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -77,6 +81,8 @@ from .appearance import appearance_mlp, appearance_mlp_check, appearance_mlp_for
 from .hexplane import hexplane_layout, HexPlaneLayout, hexplane_pack, hexplane_box, hexplane_encode, hexplane_forward, hexplane_backward, _HexPlaneFn
 from .spotless import (spotless_mask, spotless_mask_forward, spotless_mask_backward, spotless_error_stats, spotless_masked_l1,
                        spotless_masked_l1_forward, spotless_masked_l1_backward, _SpotlessMaskFn, _MaskedL1Fn)
+from .segany import (segany_mask_stats, segany_pack_membership, segany_pair_labels, segany_correspondence_loss, segany_loss_forward,
+                     segany_loss_backward, SeganyLossState, _SeganyLossFn)
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

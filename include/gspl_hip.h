@@ -1251,6 +1251,78 @@ int gspl_spotless_masked_l1_fwd(int H, int W, const float* render, const float* 
 int gspl_spotless_masked_l1_bwd(int H, int W, const float* render, const float* gt, const float* mask, const float* grad_out,
                                 float* v_render, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 24. The SegAnyGS (SAGA) training step behind the renderer (csrc/segany.hip).  PURELY ADDITIVE: six new entry points, no new struct,
+ *    nothing existing changes, GSPL_ABI_VERSION stays 39.  What `SegAnySplatting.mask_preprocess` and
+ *    `forward_with_loss_calculation` of internal/segany_splatting.py compute after the choice of the sampled pixels.  The reference's
+ *    arithmetic is torch code, so it is pinned directly (tests/segany_loss_oracle.py against tests/golden/ref_segany_loss.npz).  fp32 and
+ *    integers, device pointers only.
+ *
+ *  Limits, checked by every entry point (GSPL_ERR_INVALID_ARG):  S sampled pixels 1 .. 4096 (every count is then <= 2^24, exact in
+ *  float32);  N masks 1 .. 1024 (NW = ceil(N / 64) words, at most 16);  Ns scales 1 .. 16 (the reference has 10);  C a multiple of 4,
+ *  4 .. 64 (the route's value is 32);  every image dimension 1 .. 16384.
+ *
+ *  gspl_segany_mask_stats: masks [N, H, W], one byte per entry (non-zero = inside), read ONCE.  Two launches write
+ *      area [N] int32, ADDED to (the caller clears it): pixels per mask, integer atomics;
+ *      cover [H, W] int32: how many masks hold the pixel;
+ *      mean_size [H, W] = (sum_i mask_i(p) area_i) / (cover + 1e-9): the numerator exact in 64-bit integers and rounded once;
+ *      packed [NW, H W] u64 (the caller's scratch): the membership words of every pixel in the masks' own order.
+ *  gspl_segany_pack_membership: order [N] int32 (the permutation that sorts the masks' scales descending), pixel_index [S] int32 (flat
+ *      indices into H W) -> bits [S, NW] u64: bit i of word w = mask order[64 w + i] holds the pixel.  An index outside the image, or
+ *      an entry of `order` outside 0 .. N - 1, sets no bit.
+ *
+ *  gspl_segany_pair_labels: scale_index [Ns] int32 (the reference's `sampled_scale_index`, entry 0 holding -1; values are clamped to
+ *      -1 .. 64 NW - 1), upper [Ns] u8 (the `upper_bound` flag of each sampled scale), head [Ns, S] int32 (scratch) ->
+ *      labels [S, S] u16, BOTH triangles and the diagonal written: bit n = gt_corrs[n, h, j], by the closed form of the reference's loop
+ *          head_n(p) = the largest i <= scale_index[n] with bit i of p set, or -1
+ *          label_n(h, j) = (head_n(h) == head_n(j) >= 0)  OR  (bits_h & bits_j & {i > scale_index[n]}) != 0
+ *          an upper scale: label_n(h, j) = (bits_h & bits_j) != 0
+ *      counts [3] int32, ADDED to (the caller clears it), over the FULL S x S matrix: pairs labelled 1 at no scale, at every scale, and
+ *      the rest (the reference's consistent_negative, consistent_positive, inconsistent).  Integer atomics: exact in any order.
+ *
+ *  gspl_segany_loss_fwd: rendered [C, Hr, Wr]; pixel_index [S] into the mh x mw grid of the masks, raster order; gates [Ns, C];
+ *      labels, counts as above; a [S] > 0 (mean_size at the sampled pixels); rnd [S, S] (the reference's rand_like draw).
+ *      F [S, C] (written; the backward reads it): the bilinear sample of `rendered` at the centre of each mask pixel by the rule of
+ *        section 23 (F.interpolate, align_corners=False); the map at mask size is never made.  An index outside the grid gives zeros.
+ *      X_n[s] = (F[s] * gates[n]) / max(||F[s] * gates[n]||, 1e-12);  corr_n(h, j) = X_n[h] . X_n[j], ONE fmaf chain over c from 0,
+ *        symmetric in (h, j) by construction.
+ *      w(h, j) = (max(P / (a_h a_j), 1) - 1) / (R - 1) * 9 + 1 with P = fl(a_max a_max), R = max(P / fl(a_min a_min), 1), every operation
+ *        rounded to float32 on its own: bit-equal to the reference's min-max normalised matrix (NaN when R == 1, as there).
+ *      Over h < j:  t+ = (float(counts[2]) / 2) / float(counts[1]),  t- the same with counts[0];
+ *        M+ : (label 1 at every scale AND rnd < t+) OR any_n(corr_n < 0.75 AND label_n) OR inconsistent
+ *        M- : (label 1 at no scale AND rnd < t-)    OR any_n(corr_n > 0.5 AND NOT label_n) OR inconsistent
+ *      selected [S, S] u8: bit 0 = in M+, bit 1 = in M-; written for h < j only (the caller clears the rest).
+ *      out [3]: loss = -sum_{M+} w sum_n label_n corr_n / (Ns |M+|) + sum_{M-} w sum_n (1 - label_n) relu(corr_n) / (Ns |M-|);
+ *        cosine_pos, cosine_neg = the means of corr_n over ALL (n, h, j) of the full matrix with label 1 / label 0.  IEEE throughout:
+ *        an empty selection gives 0 / 0 = NaN.  sel_counts [2] int32 = |M+|, |M-|.
+ *      weight: NULL, or [S, S], every element written with w(h, j) (for tests).
+ *      No float atomics: one partial per 16 x 16 tile of pairs, added in tile order in float64: two runs give the same bits.
+ *  gspl_segany_loss_bwd: grad_out [1] on the device.  k_n(h, j) = grad_out [-w label_n / (Ns |M+|) [in M+]
+ *      + w (1 - label_n) [corr_n > 0] / (Ns |M-|) [in M-]];  dX_n[h] = sum_j k_n(h, j) X_n[j] over both triangles, j in index order; through
+ *      the normalisation (below its clamp the denominator is the constant 1e-12) to
+ *      v_F [S, C] and v_gates [Ns, C] (summed over s in a fixed order), both WRITTEN, the same bits on every run.  corr is recomputed
+ *      from F and gates; `selected` and `sel_counts` are the forward's; no [Ns, S, S] array is ever written.
+ *      v_rendered: NULL, or [C, Hr, Wr], ACCUMULATED into (the caller clears it): the adjoint of the bilinear sample of v_F, by fp32
+ *      atomics because samples share texels.  This scatter is OUTSIDE gspl_set_deterministic: its sums depend on arrival order in the
+ *      last bits, as gspl_hexplane_bwd's v_table does.
+ *  workspace: gspl_segany_loss_workspace_bytes(S, C, Ns) bytes for either call, aligned to 256 bytes (0: arguments out of range).
+ * ---------------------------------------------------------------------------------------- */
+int gspl_segany_mask_stats(int N, int H, int W, const uint8_t* masks, int32_t* area, int32_t* cover, float* mean_size,
+                           uint64_t* packed, void* stream);
+int gspl_segany_pack_membership(int N, int H, int W, int S, const uint8_t* masks, const int32_t* order, const int32_t* pixel_index,
+                                uint64_t* bits, void* stream);
+int gspl_segany_pair_labels(int S, int N, int Ns, const uint64_t* bits, const int32_t* scale_index, const uint8_t* upper, int32_t* head,
+                            uint16_t* labels, int32_t* counts, void* stream);
+size_t gspl_segany_loss_workspace_bytes(int S, int C, int Ns);
+int gspl_segany_loss_fwd(int S, int C, int Ns, int Hr, int Wr, int mh, int mw, const float* rendered, const int32_t* pixel_index,
+                         const float* gates, const uint16_t* labels, const int32_t* counts, const float* a, const float* rnd,
+                         float* F, float* out, int32_t* sel_counts, uint8_t* selected, float* weight, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int gspl_segany_loss_bwd(int S, int C, int Ns, int Hr, int Wr, int mh, int mw, const int32_t* pixel_index, const float* gates,
+                         const uint16_t* labels, const float* a, const uint8_t* selected, const int32_t* sel_counts, const float* F,
+                         const float* grad_out, float* v_F, float* v_gates, float* v_rendered, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
