@@ -1323,6 +1323,33 @@ int gspl_segany_loss_bwd(int S, int C, int Ns, int Hr, int Wr, int mh, int mw, c
                          const float* grad_out, float* v_F, float* v_gates, float* v_rendered, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 25. The view-dependent opacity of the Glossy-Gaussian route (csrc/glossy.hip).  PURELY ADDITIVE: two new entry points, no new
+ *    struct, nothing existing changes, GSPL_ABI_VERSION stays 39.  What `GlossyRendererModule.get_opacities`
+ *    (internal/renderers/glossy_renderer.py) and `GlossyGaussianModel.get_view_dep_opacities` (internal/models/glossy_gaussian.py)
+ *    compute: a one-channel spherical-harmonics expansion evaluated at the normalised view direction.  The reference's arithmetic is
+ *    torch code, so it is pinned directly (tests/glossy_oracle.py against tests/golden/ref_glossy.npz).  fp32, device pointers only.
+ *
+ *  means [N, 3], origin [3] (on the device), dc [N], rest [N, n_rest] (NULL if and only if n_rest == 0), degree 0 .. 4,
+ *  (degree + 1)^2 - 1 <= n_rest <= 61; anything else, or a NULL required pointer: GSPL_ERR_INVALID_ARG, nothing is launched.
+ *  N == 0 succeeds without a launch.
+ *      d = (means[n] - origin) / max(||means[n] - origin||, 1e-12)          (F.normalize: a splat AT the origin has d = 0, not NaN)
+ *      raw = C0 dc[n] + sum_{k = 1}^{(degree + 1)^2 - 1} basis_k(d) rest[n, k - 1] + 0.5
+ *      opacities[n] = min(max(raw, 0), 1)
+ *  basis_k: the polynomials of internal/utils/sh_utils.py `eval_sh_decomposed`, evaluated as written there also where d is not a
+ *  unit vector (at d = 0 the degree-4 term C4[4] (zz (35 zz - 30) + 3) is the constant 3 C4[4]).  Columns of `rest` above the active
+ *  degree are not read.  One launch.
+ *  gspl_sh_opacity_bwd: v_opacities [N] -> v_dc [N], v_rest [N, n_rest], EVERY element written (zeros in the columns above the active
+ *  degree and in the rows the clamp cut): the gradient passes where 0 <= raw <= 1, both ends included as under torch.clamp, with raw
+ *  recomputed from the inputs by the forward's own expression (nothing is saved).  A row whose incoming gradient is exactly zero is
+ *  not evaluated and its coefficients are not read.  No gradient for means or origin (the reference detaches them).  One launch, no
+ *  atomics: two runs give the same bits.
+ * ---------------------------------------------------------------------------------------- */
+int gspl_sh_opacity_fwd(int N, int degree, int n_rest, const float* means, const float* origin, const float* dc, const float* rest,
+                        float* opacities, void* stream);
+int gspl_sh_opacity_bwd(int N, int degree, int n_rest, const float* means, const float* origin, const float* dc, const float* rest,
+                        const float* v_opacities, float* v_dc, float* v_rest, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
