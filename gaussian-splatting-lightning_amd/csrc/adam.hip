@@ -25,6 +25,7 @@
 
 #include "gspl_device.h"
 #include "gspl_host.h"
+#include "gspl_rowtile.h"
 
 namespace gspl {
 
@@ -57,9 +58,6 @@ __global__ __launch_bounds__(256) void selective_adam_kernel(AdamBatchDev batch,
     const int64_t total = (int64_t)N * T.row;
     const float step = T.lr * inv_bc1;
     const int64_t nvec = total >> 2;
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    auto ntl = [](const float* base, int64_t i) { const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(base) + i); return make_float4(t.x, t.y, t.z, t.w); };
-    auto nts = [](float* base, int64_t i, const float4& q) { v4f t = {q.x, q.y, q.z, q.w}; __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(base) + i); };
     // the dense form: two 16-byte chunks per thread and iteration (8 loads in flight) and streaming (nontemporal) accesses of everything
     // that is not read again before the next step: 302 -> 257 us at 1 M Gaussians (1.65 GB: 6.4 TB/s).  The skipping form takes ONE
     // chunk: a live chunk makes two dependent round trips, and what hides the second is other waves — 44 registers and 8 waves per SIMD
@@ -93,11 +91,11 @@ __global__ __launch_bounds__(256) void selective_adam_kernel(AdamBatchDev batch,
                 for (int k = 0; k < 4; ++k) { vis[u][k] = visible ? visible[(e + k) / T.row] != 0 : true; any[u] = any[u] || vis[u][k]; }
             }
             if (any[u]) {
-                if (!SKIP) p[u] = ntl(T.p, i);
-                if (!use_rows || has_grad(i << 2)) g[u] = ntl(T.g, i);
+                if (!SKIP) p[u] = load16_nt(T.p, i);
+                if (!use_rows || has_grad(i << 2)) g[u] = load16_nt(T.g, i);
                 else g[u] = make_float4(zero, zero, zero, zero);
-                m[u] = ntl(T.m, i);
-                v[u] = ntl(T.v, i);
+                m[u] = load16_nt(T.m, i);
+                v[u] = load16_nt(T.v, i);
             }
         }
         if (SKIP) {
@@ -106,7 +104,7 @@ __global__ __launch_bounds__(256) void selective_adam_kernel(AdamBatchDev batch,
                 if (!any[u]) continue;
                 if (still(vis[u][0], g[u].x, m[u].x, v[u].x) && still(vis[u][1], g[u].y, m[u].y, v[u].y) &&
                     still(vis[u][2], g[u].z, m[u].z, v[u].z) && still(vis[u][3], g[u].w, m[u].w, v[u].w)) any[u] = false;
-                else p[u] = ntl(T.p, i0 + u * stride);
+                else p[u] = load16_nt(T.p, i0 + u * stride);
             }
         }
 #pragma unroll
@@ -118,8 +116,8 @@ __global__ __launch_bounds__(256) void selective_adam_kernel(AdamBatchDev batch,
             if (vis[u][2]) adam_elem(p[u].z, g[u].z, m[u].z, v[u].z, step, b1, b2, inv_bc2, eps);
             if (vis[u][3]) adam_elem(p[u].w, g[u].w, m[u].w, v[u].w, step, b1, b2, inv_bc2, eps);
             reinterpret_cast<float4*>(T.p)[i] = p[u];
-            nts(T.m, i, m[u]);
-            nts(T.v, i, v[u]);
+            store16_nt(T.m, i, m[u]);
+            store16_nt(T.v, i, v[u]);
         }
     }
     // tail (total not a multiple of 4)

@@ -14,6 +14,7 @@
 //   * tv_partials_kernel + tv_final_kernel: the TV loss as a fixed two-level sum; tv_bwd_kernel: its three-point stencil.
 #include "gspl_device.h"
 #include "gspl_host.h"
+#include "gspl_reduce.h"
 
 namespace gspl {
 namespace {
@@ -324,23 +325,12 @@ __device__ inline float tv_elem(const float* __restrict__ x, int64_t i, const Tv
     return s;
 }
 
-// fixed-order sum of the workgroup's values (lanes by xor butterfly, then the four waves in order); thread 0 gets the sum
-__device__ inline float block_sum(float v, float* sh) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < kT / 64; ++w) s += sh[w];
-    return s;
-}
-
+// (the sums: block_sum of gspl_reduce.h, lanes by xor butterfly, then the four waves in order)
 __global__ __launch_bounds__(kT) void tv_partials_kernel(Tv T, const float* __restrict__ x, float* __restrict__ partials) {
     __shared__ float sh[kT / 64];
     float a = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < T.n; i += (int64_t)gridDim.x * kT) a += tv_elem(x, i, T);
-    const float s = block_sum(a, sh);
+    const float s = block_sum<kT>(a, sh);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
@@ -348,7 +338,7 @@ __global__ __launch_bounds__(kT) void tv_final_kernel(int n_partials, float inv_
     __shared__ float sh[kT / 64];
     float a = 0.f;
     for (int j = threadIdx.x; j < n_partials; j += kT) a += partials[j];
-    const float s = block_sum(a, sh);
+    const float s = block_sum<kT>(a, sh);
     if (threadIdx.x == 0) out[0] = s * inv_n;
 }
 

@@ -572,7 +572,7 @@ int bin_depth_header(int N, int n_tiles, void* count_workspace, ZeroJob& job) {
     if (rc != GSPL_OK) return rc;
     job.p = (uint4*)((char*)count_workspace + w.sort1_off);
     job.n16 = (uint32_t)(w.depth.header_bytes / 16);
-    return (w.depth.header_bytes % 16 || ((uintptr_t)job.p & 15u)) ? fail_arg("bin_depth_header: not 16-byte aligned") : GSPL_OK;
+    return (w.depth.header_bytes % 16 || !aligned16(job.p)) ? fail_arg("bin_depth_header: not 16-byte aligned") : GSPL_OK;
 }
 int bin_tile_header(int N, int64_t capacity, int n_tiles, void* workspace, ZeroJob& job) {
     BinWorkspace w;
@@ -580,7 +580,7 @@ int bin_tile_header(int N, int64_t capacity, int n_tiles, void* workspace, ZeroJ
     if (rc != GSPL_OK) return rc;
     job.p = (uint4*)((char*)workspace + w.sort2_off);
     job.n16 = (uint32_t)(w.tile.header_bytes / 16);
-    return (w.tile.header_bytes % 16 || ((uintptr_t)job.p & 15u)) ? fail_arg("bin_tile_header: not 16-byte aligned") : GSPL_OK;
+    return (w.tile.header_bytes % 16 || !aligned16(job.p)) ? fail_arg("bin_tile_header: not 16-byte aligned") : GSPL_OK;
 }
 }  // namespace gspl
 

@@ -9,22 +9,21 @@
 // A `rest` row is 4 n_rest bytes (60 for degree 3): a lane-per-row read would touch 30 cache lines per wave instruction.  As in sh.hip
 // a workgroup streams its 256 rows as one flat coalesced copy into LDS rows of ODD stride (lane r then reads row r without a bank
 // conflict), and the backward stores its gradient rows the same way in reverse.  No atomics, no scratch, nothing saved by the forward.
-// (The copies are this file's own: sh.hip's tile_load / tile_store are tied to its block and unroll macros, and the copy here also
-// leaves out the columns above the active degree and the rows without an incoming gradient.)
+// (tile_load / tile_store of gspl_rowtile.h, shared with sh.hip; tile_load's PART form leaves out the columns above the active degree
+// and the rows without an incoming gradient.)
 //
 // Contraction as the language defines it: both kernels evaluate `raw` through the one function below and must agree on its bits (the
 // backward decides the clamp on the value it recomputes).
 #pragma clang fp contract(on)
 #include "gspl_device.h"
 #include "gspl_host.h"
+#include "gspl_rowtile.h"
 
 namespace gspl {
 
 static constexpr int GLOSSY_BLOCK = 256;          // rows (= threads) per workgroup
 static constexpr int GLOSSY_MAX_REST = 61;        // the backward's flags + 256 rows x 61 floats + the block vote's 256 bytes fit 64 KiB
                                                   // of LDS (the reference's widest row is 24)
-
-typedef float glossy_v4f __attribute__((ext_vector_type(4)));
 
 // d = v / max(|v|, 1e-12) (F.normalize: the zero vector stays zero), then the basis values b[0 .. K)
 template <int DEG>
@@ -44,67 +43,6 @@ __device__ __forceinline__ float glossy_raw(const float* b, float dc, const floa
     return acc + 0.5f;
 }
 
-// The first `used` columns of `rows` rows of `rs` floats -> LDS rows of stride ls.  used == rs: the rows are one contiguous run, copied
-// flat, 16 bytes per lane when `vec_ok`; used < rs (columns above the active degree): runs of `used` floats, the rest is not read.
-// live: NULL, or one flag per row in LDS: rows without a flag are not read (a 16-byte piece is read when either of the two rows it can
-// touch has one; used >= 3 there, so it touches no third).
-__device__ __forceinline__ void glossy_stage(const float* __restrict__ g, int rows, int rs, int used, int ls, float* lds, bool vec_ok,
-                                             const int* live) {
-    const int t = threadIdx.x;
-    const float inv_used = 1.f / (float)used;
-    const int total = rows * used;
-    int done = 0;
-    if (vec_ok && used == rs) {
-        const int n4 = total >> 2;
-        for (int e4 = t; e4 < n4; e4 += GLOSSY_BLOCK) {
-            const int e = e4 * 4;
-            const int first = (int)(((float)e + 0.5f) * inv_used), last = (int)(((float)(e + 3) + 0.5f) * inv_used);
-            if (live && !(live[first] | live[last])) continue;
-            const glossy_v4f v = __builtin_nontemporal_load(reinterpret_cast<const glossy_v4f*>(g) + e4);
-            const float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int row = (int)(((float)(e + k) + 0.5f) * inv_used);
-                lds[row * ls + (e + k - row * used)] = vv[k];
-            }
-        }
-        done = n4 << 2;
-    }
-    for (int e = done + t; e < total; e += GLOSSY_BLOCK) {
-        const int row = (int)(((float)e + 0.5f) * inv_used);
-        if (live && !live[row]) continue;
-        const int col = e - row * used;
-        lds[row * ls + col] = g[(int64_t)row * rs + col];
-    }
-}
-
-// LDS rows of stride ls -> `rows` contiguous rows of rs floats
-__device__ __forceinline__ void glossy_unstage(float* __restrict__ g, int rows, int rs, int ls, const float* lds, bool vec_ok) {
-    const int t = threadIdx.x;
-    const float inv_rs = 1.f / (float)rs;
-    const int total = rows * rs;
-    int done = 0;
-    if (vec_ok) {
-        const int n4 = total >> 2;
-        for (int e4 = t; e4 < n4; e4 += GLOSSY_BLOCK) {
-            float vv[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int e = e4 * 4 + k;
-                const int row = (int)(((float)e + 0.5f) * inv_rs);
-                vv[k] = lds[row * ls + (e - row * rs)];
-            }
-            const glossy_v4f v = {vv[0], vv[1], vv[2], vv[3]};
-            __builtin_nontemporal_store(v, reinterpret_cast<glossy_v4f*>(g) + e4);
-        }
-        done = n4 << 2;
-    }
-    for (int e = done + t; e < total; e += GLOSSY_BLOCK) {
-        const int row = (int)(((float)e + 0.5f) * inv_rs);
-        g[e] = lds[row * ls + (e - row * rs)];
-    }
-}
-
 template <int DEG>
 __global__ __launch_bounds__(GLOSSY_BLOCK) void sh_opacity_fwd_kernel(
     int N, int n_rest, const float* __restrict__ means, const float* __restrict__ origin, const float* __restrict__ dc,
@@ -115,7 +53,7 @@ __global__ __launch_bounds__(GLOSSY_BLOCK) void sh_opacity_fwd_kernel(
     const int64_t n0 = (int64_t)blockIdx.x * GLOSSY_BLOCK;
     const int rows = (int)min((int64_t)GLOSSY_BLOCK, (int64_t)N - n0);
     if (DEG > 0) {
-        glossy_stage(rest + n0 * n_rest, rows, n_rest, K - 1, ls, lds, vec_ok != 0, nullptr);
+        tile_load<GLOSSY_BLOCK, 1, true>(rest + n0 * n_rest, rows, n_rest, ls, 1.f / (float)(K - 1), lds, vec_ok != 0, K - 1);
         __syncthreads();
     }
     const int r = threadIdx.x;
@@ -148,7 +86,7 @@ __global__ __launch_bounds__(GLOSSY_BLOCK) void sh_opacity_bwd_kernel(
     live[r] = mine;
     const int any = __syncthreads_or(mine);
     if (DEG > 0 && any) {
-        glossy_stage(rest + n0 * n_rest, rows, n_rest, K - 1, ls, tile, vec_in != 0, live);
+        tile_load<GLOSSY_BLOCK, 1, true>(rest + n0 * n_rest, rows, n_rest, ls, 1.f / (float)(K - 1), tile, vec_in != 0, K - 1, live);
         __syncthreads();
     }
     if (r < rows) {
@@ -170,11 +108,9 @@ __global__ __launch_bounds__(GLOSSY_BLOCK) void sh_opacity_bwd_kernel(
     }
     if (n_rest > 0) {
         __syncthreads();
-        glossy_unstage(v_rest + n0 * n_rest, rows, n_rest, ls, tile, vec_out != 0);
+        tile_store<GLOSSY_BLOCK>(v_rest + n0 * n_rest, rows, n_rest, ls, 1.f / (float)n_rest, tile, vec_out != 0);
     }
 }
-
-static inline bool glossy_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 static int glossy_check(const char* who, int N, int degree, int n_rest) {
     if (N < 0 || degree < 0 || degree > 4) return fail_arg(who);
@@ -192,16 +128,13 @@ extern "C" int gspl_sh_opacity_fwd(int N, int degree, int n_rest, const float* m
     if (!means || !origin || !dc || !opacities || ((n_rest > 0) != (rest != nullptr))) return fail_arg("sh_opacity_fwd: NULL required pointer (rest is NULL iff n_rest == 0)");
     const int K = (degree + 1) * (degree + 1);
     // every block starts 256 n_rest floats further on, a multiple of 16 bytes: only the base matters
-    const int vec_ok = (degree > 0 && glossy_aligned16(rest)) ? 1 : 0;
+    const int vec_ok = (degree > 0 && aligned16(rest)) ? 1 : 0;
     const size_t lds_bytes = degree > 0 ? (size_t)GLOSSY_BLOCK * ((K - 1) | 1) * sizeof(float) : 0;
     const int grid = (int)(((int64_t)N + GLOSSY_BLOCK - 1) / GLOSSY_BLOCK);
-#define GSPL_GLOSSY_FWD(DEG)                                                                                                        \
-    case DEG:                                                                                                                       \
-        hipLaunchKernelGGL(sh_opacity_fwd_kernel<DEG>, dim3(grid), dim3(GLOSSY_BLOCK), lds_bytes, (hipStream_t)stream, N, n_rest,   \
-                           means, origin, dc, rest, vec_ok, opacities);                                                            \
-        break;
-    switch (degree) { GSPL_GLOSSY_FWD(0) GSPL_GLOSSY_FWD(1) GSPL_GLOSSY_FWD(2) GSPL_GLOSSY_FWD(3) GSPL_GLOSSY_FWD(4) }
-#undef GSPL_GLOSSY_FWD
+    dispatch_int<0, 1, 2, 3, 4>(degree, [&](auto deg) {
+        hipLaunchKernelGGL(sh_opacity_fwd_kernel<decltype(deg)::value>, dim3(grid), dim3(GLOSSY_BLOCK), lds_bytes, (hipStream_t)stream, N, n_rest,
+                           means, origin, dc, rest, vec_ok, opacities);
+    });
     return check_launch("sh_opacity_fwd");
 }
 
@@ -212,16 +145,13 @@ extern "C" int gspl_sh_opacity_bwd(int N, int degree, int n_rest, const float* m
     if (N == 0) return GSPL_OK;
     if (!means || !origin || !dc || !v_opacities || !v_dc || ((n_rest > 0) != (rest != nullptr)) || ((n_rest > 0) != (v_rest != nullptr)))
         return fail_arg("sh_opacity_bwd: NULL required pointer (rest and v_rest are NULL iff n_rest == 0)");
-    const int vec_in = (degree > 0 && glossy_aligned16(rest)) ? 1 : 0;
-    const int vec_out = (n_rest > 0 && glossy_aligned16(v_rest)) ? 1 : 0;
+    const int vec_in = (degree > 0 && aligned16(rest)) ? 1 : 0;
+    const int vec_out = (n_rest > 0 && aligned16(v_rest)) ? 1 : 0;
     const size_t lds_bytes = (size_t)GLOSSY_BLOCK * (1 + (n_rest | 1)) * sizeof(float);      // 62 KiB at n_rest = 61
     const int grid = (int)(((int64_t)N + GLOSSY_BLOCK - 1) / GLOSSY_BLOCK);
-#define GSPL_GLOSSY_BWD(DEG)                                                                                                        \
-    case DEG:                                                                                                                       \
-        hipLaunchKernelGGL(sh_opacity_bwd_kernel<DEG>, dim3(grid), dim3(GLOSSY_BLOCK), lds_bytes, (hipStream_t)stream, N, n_rest,   \
-                           means, origin, dc, rest, v_opacities, vec_in, vec_out, v_dc, v_rest);                                    \
-        break;
-    switch (degree) { GSPL_GLOSSY_BWD(0) GSPL_GLOSSY_BWD(1) GSPL_GLOSSY_BWD(2) GSPL_GLOSSY_BWD(3) GSPL_GLOSSY_BWD(4) }
-#undef GSPL_GLOSSY_BWD
+    dispatch_int<0, 1, 2, 3, 4>(degree, [&](auto deg) {
+        hipLaunchKernelGGL(sh_opacity_bwd_kernel<decltype(deg)::value>, dim3(grid), dim3(GLOSSY_BLOCK), lds_bytes, (hipStream_t)stream, N, n_rest,
+                           means, origin, dc, rest, v_opacities, vec_in, vec_out, v_dc, v_rest);
+    });
     return check_launch("sh_opacity_bwd");
 }

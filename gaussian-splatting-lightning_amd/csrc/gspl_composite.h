@@ -7,6 +7,7 @@
 #pragma once
 #include "gspl_device.h"
 #include "gspl_host.h"
+#include "gspl_rowtile.h"
 
 namespace gspl {
 
@@ -320,16 +321,13 @@ struct FillJob {
 };
 template <int NT>
 __device__ __forceinline__ void zero_fill_body(const FillJob& job, unsigned block, unsigned blocks) {
-    typedef float v4f __attribute__((ext_vector_type(4)));
     const uint64_t tid = (uint64_t)block * NT + threadIdx.x, stride = (uint64_t)blocks * NT;
     for (int k = 0; k < job.count; ++k) {
         float* p = job.a[k].p;
         const uint64_t n = job.a[k].n;
         const uint64_t head = min(n, (uint64_t)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2));
         const uint64_t n4 = (n - head) >> 2, tail0 = head + (n4 << 2);
-        v4f* q = reinterpret_cast<v4f*>(p + head);
-        const v4f z = {0.f, 0.f, 0.f, 0.f};
-        for (uint64_t i = tid; i < n4; i += stride) __builtin_nontemporal_store(z, q + i);
+        for (uint64_t i = tid; i < n4; i += stride) store16_nt(p + head, i, make_float4(0.f, 0.f, 0.f, 0.f));
         if (tid < head) p[tid] = 0.f;
         if (tid < n - tail0) p[tail0 + tid] = 0.f;
     }
@@ -360,14 +358,7 @@ int composite_bwd_packed_impl(int N, int D, int mode, int layout, const Composit
 template <class F>
 static int dispatch_composite(int D, int mode, int layout, F&& f) {
     auto with_d = [&](auto mode_c, auto chw_c) -> int {
-        switch (D) {
-            case 1: return f(std::integral_constant<int, 1>{}, mode_c, chw_c);
-            case 2: return f(std::integral_constant<int, 2>{}, mode_c, chw_c);
-            case 3: return f(std::integral_constant<int, 3>{}, mode_c, chw_c);
-            case 4: return f(std::integral_constant<int, 4>{}, mode_c, chw_c);
-            case 8: return f(std::integral_constant<int, 8>{}, mode_c, chw_c);
-        }
-        return GSPL_ERR_UNSUPPORTED;
+        return dispatch_int<1, 2, 3, 4, 8>(D, [&](auto d) -> int { return f(d, mode_c, chw_c); }, (int)GSPL_ERR_UNSUPPORTED);
     };
     return dispatch_bools([&](auto inria, auto chw) { return with_d(std::integral_constant<int, decltype(inria)::value ? GSPL_MODE_INRIA : GSPL_MODE_GSPLAT>{}, chw); },
                           mode != GSPL_MODE_GSPLAT, layout != GSPL_LAYOUT_HWC);

@@ -34,6 +34,8 @@ inline int check_hip(hipError_t e, const char* where) {
 }
 
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+// what the 16-byte accesses of the kernels ask of a base pointer (NULL passes: a caller for which NULL is no array says so itself)
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // One block carved into regions in the order they are taken, each starting on a 256-byte boundary; `off` ends as the block's size.
 struct Carve {
@@ -48,6 +50,21 @@ template <class F, class... Bs>
 auto dispatch_bools(F&& f, bool b, Bs... rest) {
     auto bound = [&](auto c) { return dispatch_bools([&](auto... cs) { return f(c, cs...); }, rest...); };
     return b ? bound(std::true_type{}) : bound(std::false_type{});
+}
+
+// A run-time int as a template argument: f(std::integral_constant<int, V>) for the V of the list that equals `value`, and its result.
+// A value outside the list is the call site's choice: with `otherwise` given, f is not called and `otherwise` returned; without, the
+// LAST V of the list takes every other value (the caller has refused them).
+template <int V0, int... Vs, class F, class R>
+R dispatch_int(int value, F&& f, R otherwise) {
+    if (value == V0) return f(std::integral_constant<int, V0>{});
+    if constexpr (sizeof...(Vs) == 0) return otherwise;
+    else return dispatch_int<Vs...>(value, f, otherwise);
+}
+template <int V0, int... Vs, class F>
+auto dispatch_int(int value, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+    else return value == V0 ? f(std::integral_constant<int, V0>{}) : dispatch_int<Vs...>(value, f);
 }
 
 // A kernel templated on the compositing mode: f(MODE) gets it as a std::integral_constant (the caller has refused every other mode;

@@ -222,15 +222,7 @@ __global__ __launch_bounds__(HG_BLOCK) void hashgrid_bwd_x_kernel(int N, int L, 
 // f(std::integral_constant<int, D>, std::integral_constant<int, F>) for the built (D, F); the caller has checked both
 template <class Fn>
 static int hg_dispatch(int D, int F, Fn&& fn) {
-    auto with_d = [&](auto d) {
-        switch (F) {
-            case 1: return fn(d, std::integral_constant<int, 1>{});
-            case 2: return fn(d, std::integral_constant<int, 2>{});
-            case 4: return fn(d, std::integral_constant<int, 4>{});
-            default: return fn(d, std::integral_constant<int, 8>{});
-        }
-    };
-    return D == 2 ? with_d(std::integral_constant<int, 2>{}) : with_d(std::integral_constant<int, 3>{});
+    return dispatch_int<2, 3>(D, [&](auto d) { return dispatch_int<1, 2, 4, 8>(F, [&](auto f) { return fn(d, f); }); });
 }
 
 // The argument checks both entries share; fills `lv`.  scales, resolutions [L] and offsets [L + 1] are HOST arrays.

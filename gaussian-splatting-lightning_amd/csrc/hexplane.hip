@@ -243,16 +243,6 @@ __global__ __launch_bounds__(HP_BLOCK) void hexplane_bwd_x_kernel(int N, int L, 
     }
 }
 
-template <class Fn>
-static int hp_dispatch(int F, Fn&& fn) {
-    switch (F) {
-        case 8: return fn(std::integral_constant<int, 8>{});
-        case 16: return fn(std::integral_constant<int, 16>{});
-        case 32: return fn(std::integral_constant<int, 32>{});
-        default: return fn(std::integral_constant<int, 64>{});
-    }
-}
-
 // The argument checks both entries share; fills `tb`.  resolutions [L, 4], offsets [6 L + 1] and box [6] are HOST arrays.  A plane's
 // rows must be exactly R_a R_b, so no clamped index can address outside the table.
 static int hp_table(const char* who, int N, int F, int L, const uint32_t* resolutions, const uint32_t* offsets, const float* box, HpTable& tb) {
@@ -279,8 +269,6 @@ static int hp_table(const char* who, int N, int F, int L, const uint32_t* resolu
     return GSPL_OK;
 }
 
-static bool hp_aligned(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
 }  // namespace gspl
 
 using namespace gspl;
@@ -291,8 +279,8 @@ extern "C" int gspl_hexplane_fwd(int N, int F, int L, const uint32_t* resolution
     if (const int rc = hp_table("gspl_hexplane_fwd", N, F, L, resolutions, offsets, box, tb)) return rc;
     if (N == 0) return GSPL_OK;
     if (!x || !table || !out) return fail_arg("gspl_hexplane_fwd");
-    if (!hp_aligned(table) || !hp_aligned(out)) { set_error("gspl_hexplane_fwd", "table and out must be aligned to 16 bytes"); return GSPL_ERR_INVALID_ARG; }
-    return hp_dispatch(F, [&](auto f) {
+    if (!aligned16(table) || !aligned16(out)) { set_error("gspl_hexplane_fwd", "table and out must be aligned to 16 bytes"); return GSPL_ERR_INVALID_ARG; }
+    return dispatch_int<8, 16, 32, 64>(F, [&](auto f) {      // (hp_table has refused every other F)
         constexpr int points = HP_BLOCK / (decltype(f)::value / 4);
         hipLaunchKernelGGL((hexplane_fwd_kernel<decltype(f)::value>), dim3((N + points - 1) / points, L), dim3(HP_BLOCK), 0, (hipStream_t)stream,
                            N, L, tb, x, t, t_uniform, table, out);
@@ -307,8 +295,8 @@ extern "C" int gspl_hexplane_bwd(int N, int F, int L, const uint32_t* resolution
     if (const int rc = hp_table("gspl_hexplane_bwd", N, F, L, resolutions, offsets, box, tb)) return rc;
     if (N == 0) return GSPL_OK;
     if (!x || !table || !v_out || (!v_table && !v_x)) return fail_arg("gspl_hexplane_bwd");
-    if (!hp_aligned(table) || !hp_aligned(v_out)) { set_error("gspl_hexplane_bwd", "table and v_out must be aligned to 16 bytes"); return GSPL_ERR_INVALID_ARG; }
-    return hp_dispatch(F, [&](auto f) {
+    if (!aligned16(table) || !aligned16(v_out)) { set_error("gspl_hexplane_bwd", "table and v_out must be aligned to 16 bytes"); return GSPL_ERR_INVALID_ARG; }
+    return dispatch_int<8, 16, 32, 64>(F, [&](auto f) {      // (hp_table has refused every other F)
         if (v_table) {
             constexpr int points = HP_BLOCK / decltype(f)::value;
             hipLaunchKernelGGL((hexplane_bwd_table_kernel<decltype(f)::value>), dim3((N + points - 1) / points, L), dim3(HP_BLOCK), 0, (hipStream_t)stream,

@@ -23,6 +23,7 @@
 #pragma clang fp contract(on)
 #include "gspl_device.h"
 #include "gspl_host.h"
+#include "gspl_rowtile.h"
 
 namespace gspl {
 
@@ -46,8 +47,7 @@ __device__ __forceinline__ void rows_to_lds(const float* __restrict__ g, int64_t
     const int total = rows * W;
     if ((reinterpret_cast<uintptr_t>(base) & 15) == 0) {
         const int n4 = total >> 2;
-        typedef float v4f_ __attribute__((ext_vector_type(4)));
-        for (int i = threadIdx.x; i < n4; i += NT) reinterpret_cast<v4f_*>(s)[i] = __builtin_nontemporal_load(reinterpret_cast<const v4f_*>(base) + i);
+        for (int i = threadIdx.x; i < n4; i += NT) reinterpret_cast<float4*>(s)[i] = load16_nt(base, i);
         for (int i = (n4 << 2) + threadIdx.x; i < total; i += NT) s[i] = base[i];
     } else {
         for (int i = threadIdx.x; i < total; i += NT) s[i] = base[i];
@@ -748,12 +748,7 @@ int inria_preprocess_bwd_impl(int N, const InriaParams& p, const InriaCamera& ca
                                v_opacities, opac_act, pre, stats, grad_rows, tail);
         };
         dispatch_bools([&](auto R) {
-            switch (degree) {
-                case 0: launch(R, std::integral_constant<int, 0>{}); break;
-                case 1: launch(R, std::integral_constant<int, 1>{}); break;
-                case 2: launch(R, std::integral_constant<int, 2>{}); break;
-                default: launch(R, std::integral_constant<int, 3>{}); break;
-            }
+            dispatch_int<0, 1, 2, 3>(degree, [&](auto deg) { launch(R, deg); });
         }, raw);
         return check_launch("inria_preprocess_bwd(one-launch tail)");
     }

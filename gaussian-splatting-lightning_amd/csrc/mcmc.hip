@@ -200,7 +200,8 @@ __global__ __launch_bounds__(kBlock) void randn_kernel(int N, uint64_t seed, uin
 __device__ inline float reg_o(float o, bool raw) { return raw ? 1.f / (1.f + expf(-o)) : fabsf(o); }
 __device__ inline float reg_s(float s, bool raw) { return raw ? expf(s) : fabsf(s); }
 
-// fixed-order tree sum of the workgroup's values a[0..kBlock)
+// fixed-order tree sum of the workgroup's values a[0..kBlock).  The one workgroup sum that is not block_sum of gspl_reduce.h: an LDS tree
+// associates differently from a butterfly and a chain over the waves, and the last bits of gspl_mcmc_reg_fwd's two scalars are its.
 __device__ inline void block_sum2(float* a, float* b) {
 #pragma unroll
     for (int w = kBlock / 2; w > 0; w >>= 1) {
@@ -267,7 +268,6 @@ __global__ __launch_bounds__(kBlock) void reg_bwd_kernel(int N, int raw, const f
     }
 }
 
-inline bool aligned16(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 }  // namespace gspl
@@ -290,6 +290,7 @@ extern "C" int gspl_mcmc_perturb_means(int N, int raw, float* means, const float
     if (N == 0) return GSPL_OK;
     if (!means || !scales || !rotations || !opacities) return fail_arg("mcmc_perturb_means: NULL pointer");
     if (!noise && (offset & 3u)) return fail_arg("mcmc_perturb_means: the generator offset must be a multiple of 4");
+    // (noise may be NULL: the kernel then draws its own, and NULL passes aligned16)
     const int vec = aligned16(means) && aligned16(scales) && aligned16(rotations) && aligned16(opacities) && aligned16(noise);
     const int64_t threads = ((int64_t)N + 3) / 4;
     const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock));

@@ -15,6 +15,7 @@
 #include <cfloat>
 #include "gspl_device.h"
 #include "gspl_host.h"
+#include "gspl_reduce.h"
 
 namespace gspl {
 namespace {
@@ -239,22 +240,7 @@ __global__ __launch_bounds__(kTX * kTY) void surfel_maps_bwd_kernel(int H, int W
     v_allmap[6 * P + p] = 0.f;
 }
 
-// ---- the regulariser sums --------------------------------------------------------------------------------------------------------------
-// fixed-order sum of the workgroup's values (lanes by xor butterfly, then the four waves in order); thread 0 gets the sum
-__device__ inline float block_sum(float v, float* sh) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-    if (threadIdx.x == 0) {
-        s = sh[0];
-        for (int w = 1; w < kT / 64; ++w) s += sh[w];
-    }
-    __syncthreads();
-    return s;
-}
-
+// ---- the regulariser sums (block_sum of gspl_reduce.h: lanes by xor butterfly, then the four waves in order) ---------------------------
 __global__ __launch_bounds__(kT) void reg_partials_kernel(int64_t P, const float* __restrict__ a, const float* __restrict__ b,
                                                           const float* __restrict__ dist, float* __restrict__ partials) {
     __shared__ float sh[kT / 64];
@@ -266,7 +252,7 @@ __global__ __launch_bounds__(kT) void reg_partials_kernel(int64_t P, const float
         sn += 1.f - (a[p] * b[p] + a[P + p] * b[P + p] + a[2 * P + p] * b[2 * P + p]);
         if (dist) sd += dist[p];
     }
-    const float tn = block_sum(sn, sh), td = block_sum(sd, sh);
+    const float tn = block_sum<kT>(sn, sh), td = block_sum<kT>(sd, sh);
     if (threadIdx.x == 0) {
         partials[2 * blockIdx.x] = tn;
         partials[2 * blockIdx.x + 1] = td;
@@ -280,7 +266,7 @@ __global__ __launch_bounds__(kT) void reg_final_kernel(int n_partials, float inv
         sn += partials[2 * j];
         sd += partials[2 * j + 1];
     }
-    const float tn = block_sum(sn, sh), td = block_sum(sd, sh);
+    const float tn = block_sum<kT>(sn, sh), td = block_sum<kT>(sd, sh);
     if (threadIdx.x == 0) {
         out[0] = tn * inv_p;
         out[1] = td * inv_p;

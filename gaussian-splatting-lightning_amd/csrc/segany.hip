@@ -20,6 +20,7 @@
 //            with float atomics (samples share texels): the only sum here whose last bits depend on arrival order.
 #include <cstdint>
 #include "gspl_host.h"
+#include "gspl_reduce.h"
 #include "gspl_resample.h"
 
 namespace gspl {
@@ -34,22 +35,6 @@ constexpr int SGA_MAX_C = 64;
 constexpr int SGA_MAX_DIM = 16384;
 constexpr int SGA_TILE = 16;           // pairs per side of a loss tile
 constexpr int SGA_LH = 16, SGA_LJ = 64;      // a label tile: 16 rows of 64 pairs
-
-__device__ __forceinline__ float sga_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ int sga_wave_sum(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double sga_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // ---- stage 1 -------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(SGA_BLOCK) void sga_cover_kernel(int N, int64_t P, const uint8_t* __restrict__ masks, int32_t* __restrict__ area,
@@ -199,7 +184,7 @@ __global__ __launch_bounds__(SGA_BLOCK) void sga_label_kernel(int S, int NW, int
         n_pos += lab == all;
         n_inc += lab != 0 && lab != all;
     }
-    n_neg = sga_wave_sum(n_neg), n_pos = sga_wave_sum(n_pos), n_inc = sga_wave_sum(n_inc);
+    n_neg = wave_sum(n_neg), n_pos = wave_sum(n_pos), n_inc = wave_sum(n_inc);
     if (jl == 0) {
         atomicAdd(&total[0], n_neg);
         atomicAdd(&total[1], n_pos);
@@ -309,25 +294,6 @@ __device__ __forceinline__ SgaThresholds sga_thresholds(const int32_t* __restric
     return SgaThresholds{half / (float)counts[1], half / (float)counts[0]};
 }
 
-__device__ __forceinline__ float sga_block_sum(float v, float* sh) {      // lanes by butterfly, then the four waves in order: thread 0 gets the sum
-    v = sga_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-    if (threadIdx.x == 0) s = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-    __syncthreads();
-    return s;
-}
-__device__ __forceinline__ int sga_block_sum(int v, int* sh) {
-    v = sga_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int s = 0;
-    if (threadIdx.x == 0) s = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return s;
-}
-
 // One 16 x 16 tile of pairs with tile row <= tile column; lane (ty, tx) owns the pair (h, j).  Partials per tile: pf [4] = the weighted
 // sums over M+ and M-, the cosine sums of label 1 and label 0; pi [4] = |M+|, |M-|, the two cosine counts.
 __global__ __launch_bounds__(SGA_BLOCK) void sga_pair_kernel(int S, int C, int Ns, const float* __restrict__ X, const uint16_t* __restrict__ labels,
@@ -389,10 +355,10 @@ __global__ __launch_bounds__(SGA_BLOCK) void sga_pair_kernel(int S, int C, int N
             if (in_neg) loss_neg = w * neg_sum, n_neg = 1;
         }
     }
-    const float f0 = sga_block_sum(loss_pos, red_f), f1 = sga_block_sum(loss_neg, red_f);
-    const float f2 = sga_block_sum(cos_pos, red_f), f3 = sga_block_sum(cos_neg, red_f);
-    const int i0 = sga_block_sum(n_pos, red_i), i1 = sga_block_sum(n_neg, red_i);
-    const int i2 = sga_block_sum(n_cos_pos, red_i), i3 = sga_block_sum(n_cos_neg, red_i);
+    const float f0 = block_sum<SGA_BLOCK>(loss_pos, red_f), f1 = block_sum<SGA_BLOCK>(loss_neg, red_f);
+    const float f2 = block_sum<SGA_BLOCK>(cos_pos, red_f), f3 = block_sum<SGA_BLOCK>(cos_neg, red_f);
+    const int i0 = block_sum<SGA_BLOCK>(n_pos, red_i), i1 = block_sum<SGA_BLOCK>(n_neg, red_i);
+    const int i2 = block_sum<SGA_BLOCK>(n_cos_pos, red_i), i3 = block_sum<SGA_BLOCK>(n_cos_neg, red_i);
     if (threadIdx.x == 0) {
         const size_t at = ((size_t)bi * gridDim.x + bj) * 4;
         pf[at] = f0, pf[at + 1] = f1, pf[at + 2] = f2, pf[at + 3] = f3;
@@ -415,7 +381,7 @@ __global__ __launch_bounds__(SGA_BLOCK) void sga_final_kernel(int nt, int Ns, co
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const double v = sga_wave_sum(acc[k]);
+        const double v = wave_sum(acc[k]);
         if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = v;
     }
     __syncthreads();
@@ -532,7 +498,7 @@ __global__ __launch_bounds__(64) void sga_gates_kernel(int S, int NC, const floa
     const int o = blockIdx.x, lane = threadIdx.x;
     float acc = 0.f;
     for (int s = lane; s < S; s += 64) acc += dG[(size_t)s * NC + o];
-    acc = sga_wave_sum(acc);
+    acc = wave_sum(acc);
     if (lane == 0) v_gates[o] = acc;
 }
 

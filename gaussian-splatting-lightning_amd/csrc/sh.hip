@@ -19,6 +19,7 @@
 #pragma clang fp contract(on)
 #include "gspl_device.h"
 #include "gspl_host.h"
+#include "gspl_rowtile.h"
 
 namespace gspl {
 
@@ -74,82 +75,8 @@ __device__ __forceinline__ void sh_basis_grad(int degree, float x, float y, floa
     { const float c = 0.6258357354491761f * w[24]; gx += c * (4.f * xx * x - 12.f * x * yy); gy += c * (-12.f * xx * y + 4.f * yy * y); }
 }
 
-// The coefficient rows and their gradients are streamed once per launch: nontemporal accesses.
-typedef float sh_v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 sh_load16(const float4* p) {
-    const sh_v4f t = __builtin_nontemporal_load(reinterpret_cast<const sh_v4f*>(p));
-    return make_float4(t.x, t.y, t.z, t.w);
-}
-__device__ __forceinline__ void sh_store16(float4* p, const float4& q) {
-    const sh_v4f t = {q.x, q.y, q.z, q.w};
-    __builtin_nontemporal_store(t, reinterpret_cast<sh_v4f*>(p));
-}
-
-// Flat coalesced copy of `rows` rows x `rs` floats (contiguous in global) into LDS rows of stride ls.
-__device__ __forceinline__ void tile_load(const float* __restrict__ g, int rows, int rs, int ls, float inv_rs,
-                                          float* lds, bool vec_ok) {
-    const int total = rows * rs;
-    const int t = threadIdx.x;
-    int done = 0;
-    if (vec_ok) {
-        const int n4 = total >> 2;
-        const float4* g4 = reinterpret_cast<const float4*>(g);
-        // batches of U independent 16-B loads per lane before any LDS write: keeps U KiB per wave in flight
-        // (a load -> scatter -> load chain leaves the memory pipe idle most of the time: SQ_WAIT_ANY was 77 %)
-        constexpr int U = GSPL_SH_U;
-        for (int b4 = t; b4 < n4; b4 += SH_BLOCK * U) {
-            float4 v[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int e4 = b4 + u * SH_BLOCK;
-                v[u] = (e4 < n4) ? sh_load16(g4 + e4) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int e4 = b4 + u * SH_BLOCK;
-                if (e4 < n4) {
-                    const float vv[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int e = e4 * 4 + k;
-                        const int row = (int)(((float)e + 0.5f) * inv_rs);
-                        lds[row * ls + (e - row * rs)] = vv[k];
-                    }
-                }
-            }
-        }
-        done = n4 << 2;
-    }
-    for (int e = done + t; e < total; e += SH_BLOCK) {
-        const int row = (int)(((float)e + 0.5f) * inv_rs);
-        lds[row * ls + (e - row * rs)] = g[e];
-    }
-}
-__device__ __forceinline__ void tile_store(float* __restrict__ g, int rows, int rs, int ls, float inv_rs,
-                                           const float* lds, bool vec_ok) {
-    const int total = rows * rs;
-    const int t = threadIdx.x;
-    int done = 0;
-    if (vec_ok) {
-        const int n4 = total >> 2;
-        float4* g4 = reinterpret_cast<float4*>(g);
-        for (int e4 = t; e4 < n4; e4 += SH_BLOCK) {
-            float vv[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int e = e4 * 4 + k;
-                const int row = (int)(((float)e + 0.5f) * inv_rs);
-                vv[k] = lds[row * ls + (e - row * rs)];
-            }
-            sh_store16(g4 + e4, make_float4(vv[0], vv[1], vv[2], vv[3]));
-        }
-        done = n4 << 2;
-    }
-    for (int e = done + t; e < total; e += SH_BLOCK) {
-        const int row = (int)(((float)e + 0.5f) * inv_rs);
-        g[e] = lds[row * ls + (e - row * rs)];
-    }
-}
+// (load16_nt / store16_nt, tile_row, tile_load and tile_store: gspl_rowtile.h.  The coefficient rows and their gradients are streamed
+// once per launch; this file's tiles are SH_BLOCK rows, loaded GSPL_SH_U pieces per lane at a time.)
 
 // The Adam-applying counterpart of tile_store (backward kernels of the "update inside the backward" form): the rows of
 // LDS hold the GRADIENT of `rows` rows x `rs` floats; parameter and moments are streamed through once, flat and coalesced, 16 bytes
@@ -164,15 +91,13 @@ __device__ __forceinline__ void tile_adam(const AdamTarget& T, int64_t base, int
     if (vec_ok) {
         const int n4 = total >> 2;
         float4* p4 = reinterpret_cast<float4*>(gp);
-        float4* m4 = reinterpret_cast<float4*>(gm);
-        float4* v4 = reinterpret_cast<float4*>(gv);
         constexpr int U = GSPL_SH_ADAM_U;      // 16-byte chunks per lane and iteration: 3 U loads in flight
         for (int b4 = t; b4 < n4; b4 += U * SH_BLOCK) {
             float4 p[U], m[U], v[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int e4 = b4 + u * SH_BLOCK;
-                if (e4 < n4) { p[u] = sh_load16(p4 + e4); m[u] = sh_load16(m4 + e4); v[u] = sh_load16(v4 + e4); }
+                if (e4 < n4) { p[u] = load16_nt(gp, e4); m[u] = load16_nt(gm, e4); v[u] = load16_nt(gv, e4); }
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -182,7 +107,7 @@ __device__ __forceinline__ void tile_adam(const AdamTarget& T, int64_t base, int
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int e = e4 * 4 + k;
-                    const int row = (int)(((float)e + 0.5f) * inv_rs);
+                    const int row = tile_row(e, inv_rs);
                     g[k] = lds[row * ls + (e - row * rs)];
                 }
                 adam_elem(p[u].x, g[0], m[u].x, v[u].x, T.h);
@@ -190,14 +115,14 @@ __device__ __forceinline__ void tile_adam(const AdamTarget& T, int64_t base, int
                 adam_elem(p[u].z, g[2], m[u].z, v[u].z, T.h);
                 adam_elem(p[u].w, g[3], m[u].w, v[u].w, T.h);
                 p4[e4] = p[u];                       // read again by the next frame's colour kernel: a plain store
-                sh_store16(m4 + e4, m[u]);
-                sh_store16(v4 + e4, v[u]);
+                store16_nt(gm, e4, m[u]);
+                store16_nt(gv, e4, v[u]);
             }
         }
         done = n4 << 2;
     }
     for (int e = done + t; e < total; e += SH_BLOCK) {
-        const int row = (int)(((float)e + 0.5f) * inv_rs);
+        const int row = tile_row(e, inv_rs);
         float p = gp[e], m = gm[e], v = gv[e];
         adam_elem(p, lds[row * ls + (e - row * rs)], m, v, T.h);
         gp[e] = p; gm[e] = m; gv[e] = v;
@@ -227,7 +152,7 @@ __global__ __launch_bounds__(SH_BLOCK) void sh_fwd_kernel(
     constexpr int K = (DEG + 1) * (DEG + 1);
     if (degree > 0) {
         const float* base = tile.merged ? dc + (int64_t)n0 * tile.rs : rest + (int64_t)n0 * tile.rs;
-        tile_load(base, rows, tile.rs, tile.ls, 1.f / (float)tile.rs, lds, vec_ok != 0);
+        tile_load<SH_BLOCK, GSPL_SH_U>(base, rows, tile.rs, tile.ls, 1.f / (float)tile.rs, lds, vec_ok != 0);
         __syncthreads();
     }
     const int r = threadIdx.x;
@@ -351,7 +276,7 @@ __global__ __launch_bounds__(SH_BLOCK) void sh_bwd_kernel(
     } else if (WITH_DIRS) {      // one camera only (checked by the launcher)
         if (degree > 0) {
             const float* base = tile.merged ? dc + (int64_t)n0 * tile.rs : rest + (int64_t)n0 * tile.rs;
-            tile_load(base, rows, tile.rs, tile.ls, 1.f / (float)tile.rs, lds, vec_ok_in != 0);
+            tile_load<SH_BLOCK, GSPL_SH_U>(base, rows, tile.rs, tile.ls, 1.f / (float)tile.rs, lds, vec_ok_in != 0);
             __syncthreads();
         }
         if (r < rows) {
@@ -438,13 +363,12 @@ __global__ __launch_bounds__(SH_BLOCK) void sh_bwd_kernel(
                     for (int c = lane; c < tile.rs; c += 64) base[(int64_t)row * tile.rs + c] = lds[row * tile.ls + c];
                 }
             } else {
-                tile_store(base, rows, tile.rs, tile.ls, 1.f / (float)tile.rs, lds, vec_ok_out != 0);
+                tile_store<SH_BLOCK>(base, rows, tile.rs, tile.ls, 1.f / (float)tile.rs, lds, vec_ok_out != 0);
             }
         }
     }
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace gspl
 

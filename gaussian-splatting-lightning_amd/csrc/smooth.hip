@@ -253,7 +253,7 @@ extern "C" int gspl_smooth_features_fwd(int N, int D, int K, uint32_t mask, cons
     if (rc != GSPL_OK || N == 0) return rc;
     if (!features || !idx || !out || !mnorm) return fail_arg("smooth_features_fwd: NULL required pointer");
     const float inv_s = 1.f / (float)__builtin_popcount(mask);
-    if (D % 4 == 0 && (((uintptr_t)features | (uintptr_t)out) & 15) == 0)
+    if (D % 4 == 0 && aligned16(features) && aligned16(out))
         smooth_launch<4, 8>(true, N, D, K, mask, inv_s, features, idx, nullptr, nullptr, out, mnorm, nullptr, nullptr, (hipStream_t)stream);
     else
         smooth_launch<1, 32>(true, N, D, K, mask, inv_s, features, idx, nullptr, nullptr, out, mnorm, nullptr, nullptr, (hipStream_t)stream);
@@ -267,8 +267,7 @@ extern "C" int gspl_smooth_features_bwd(int N, int D, int K, uint32_t mask, cons
     if (rc != GSPL_OK || N == 0) return rc;
     if (!features || !row_start || !entries || !out || !mnorm || !v_out || !v_features) return fail_arg("smooth_features_bwd: NULL required pointer");
     const float inv_s = 1.f / (float)__builtin_popcount(mask);
-    const uintptr_t align = (uintptr_t)features | (uintptr_t)out | (uintptr_t)v_out | (uintptr_t)v_features;
-    if (D % 4 == 0 && (align & 15) == 0)
+    if (D % 4 == 0 && aligned16(features) && aligned16(out) && aligned16(v_out) && aligned16(v_features))
         smooth_launch<4, 8>(false, N, D, K, mask, inv_s, features, nullptr, row_start, entries, (float*)out, (float*)mnorm, v_out, v_features,
                             (hipStream_t)stream);
     else

@@ -327,7 +327,7 @@ __global__ __launch_bounds__(256) void radix_zero_kernel(uint4* __restrict__ p, 
 }
 int radix_zero(void* p, size_t bytes, void* stream) {
     if (bytes == 0) return GSPL_OK;
-    if (bytes % 16 != 0 || ((uintptr_t)p & 15u) != 0) return fail_arg("radix_zero: not 16-byte aligned");
+    if (bytes % 16 != 0 || !aligned16(p)) return fail_arg("radix_zero: not 16-byte aligned");
     const size_t n16 = bytes / 16;
     hipLaunchKernelGGL(radix_zero_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint4*)p, n16);
     return check_launch("radix_zero");

@@ -22,6 +22,7 @@
 // torch's own kernels compute it (pinned against F.interpolate's weights in tests/test_spotless_cpu.py), nothing else contracted.
 #include <cstdint>
 #include "gspl_host.h"
+#include "gspl_reduce.h"
 #include "gspl_resample.h"
 
 namespace gspl {
@@ -130,13 +131,6 @@ __global__ __launch_bounds__(SLS_BLOCK) void sls_fwd_kernel(SlsShape p, const fl
     out[(size_t)oy * OW + ox] = s;
 }
 
-// fixed butterfly over the 64 lanes: every lane gets the sum
-__device__ __forceinline__ float sls_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // the gradient that reaches mask pixel (i, j): v_out itself, or the adjoint of the second resampling gathered in a fixed order
 template <bool RESAMPLE>
 __device__ __forceinline__ float sls_incoming(const SlsShape& p, const float* __restrict__ v_out, int i, int j) {
@@ -206,7 +200,7 @@ __global__ __launch_bounds__(64) void sls_bwd_rows_kernel(SlsShape p, int ncb, c
             } else {
 #pragma unroll
                 for (int c = 0; c < SLS_HID; ++c) {
-                    const float sum = sls_wave_sum(dz[c]);
+                    const float sum = wave_sum(dz[c]);
                     if (lane == c) row[c] = sum;
                 }
             }
@@ -224,10 +218,10 @@ __global__ __launch_bounds__(64) void sls_bwd_rows_kernel(SlsShape p, int ncb, c
     float* w = pw + ((size_t)y * ncb + cb) * (SLS_HID + 1);
 #pragma unroll
     for (int c = 0; c < SLS_HID; ++c) {
-        const float sum = sls_wave_sum(sw[c]);
+        const float sum = wave_sum(sw[c]);
         if (lane == c) w[c] = sum;
     }
-    const float sum = sls_wave_sum(sb);
+    const float sum = wave_sum(sb);
     if (lane == SLS_HID) w[SLS_HID] = sum;
 }
 
@@ -242,7 +236,7 @@ __global__ __launch_bounds__(SLS_BLOCK) void sls_bwd_final_kernel(SlsShape p, in
         const int k = (int)t >> 6, lane = (int)t & 63, n = p.h0 * ncb;
         float acc = 0.f;
         for (int r = lane; r < n; r += 64) acc += pw[(size_t)r * (SLS_HID + 1) + k];
-        acc = sls_wave_sum(acc);
+        acc = wave_sum(acc);
         if (lane == 0) v_w[k] = acc;
         return;
     }
@@ -347,20 +341,7 @@ __global__ __launch_bounds__(SLS_BLOCK) void sls_error_stats_kernel(int H, int W
 // ---- the masked L1 ---------------------------------------------------------------------------------------------------------------------
 constexpr int SLS_L1_CHAIN = 8;                            // pixels per lane of a partial
 constexpr int SLS_L1_PER_PARTIAL = SLS_BLOCK * SLS_L1_CHAIN;
-
-// lanes by butterfly, then the four waves in order; thread 0 gets the sum
-__device__ __forceinline__ float sls_block_sum(float v, float* sh) {
-    v = sls_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-    if (threadIdx.x == 0) {
-        s = sh[0];
-        for (int w = 1; w < SLS_BLOCK / 64; ++w) s += sh[w];
-    }
-    __syncthreads();
-    return s;
-}
+// (block_sum of gspl_reduce.h: lanes by butterfly, then the four waves in order; thread 0 gets the sum)
 
 __global__ __launch_bounds__(SLS_BLOCK) void sls_l1_partials_kernel(int64_t P, const float* __restrict__ render, const float* __restrict__ gt,
                                                                     const float* __restrict__ mask, float* __restrict__ partials) {
@@ -373,7 +354,7 @@ __global__ __launch_bounds__(SLS_BLOCK) void sls_l1_partials_kernel(int64_t P, c
         const float d = (fabsf(render[q] - gt[q]) + fabsf(render[P + q] - gt[P + q])) + fabsf(render[2 * P + q] - gt[2 * P + q]);
         acc = fmaf(mask[q], d, acc);
     }
-    const float total = sls_block_sum(acc, sh);
+    const float total = block_sum<SLS_BLOCK>(acc, sh);
     if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
 
@@ -381,7 +362,7 @@ __global__ __launch_bounds__(SLS_BLOCK) void sls_l1_final_kernel(int n_partials,
     __shared__ float sh[SLS_BLOCK / 64];
     float acc = 0.f;
     for (int k = threadIdx.x; k < n_partials; k += SLS_BLOCK) acc += partials[k];
-    const float total = sls_block_sum(acc, sh);
+    const float total = block_sum<SLS_BLOCK>(acc, sh);
     if (threadIdx.x == 0) out[0] = total / denom;
 }
 
@@ -398,7 +379,6 @@ __global__ __launch_bounds__(SLS_BLOCK) void sls_l1_bwd_kernel(int64_t P, double
     }
 }
 
-bool sls_aligned(const void* p) { return ((uintptr_t)p % 16) == 0; }
 bool sls_dim(int n) { return n >= 2 && n <= SLS_MAX_DIM; }
 
 int sls_shape(const char* who, int h0, int w0, int mh, int mw, int H, int W, SlsShape& p) {
@@ -433,7 +413,7 @@ extern "C" int gspl_spotless_mask_fwd(int h0, int w0, int mh, int mw, int H, int
     SlsShape p;
     if (const int rc = sls_shape("gspl_spotless_mask_fwd", h0, w0, mh, mw, H, W, p)) return rc;
     if (!G || !A || !B || !w2 || !b2 || !out) return fail_arg("gspl_spotless_mask_fwd");
-    if (!sls_aligned(G) || !sls_aligned(A) || !sls_aligned(B)) { set_error("gspl_spotless_mask_fwd", "G, A and B must be aligned to 16 bytes"); return GSPL_ERR_INVALID_ARG; }
+    if (!aligned16(G) || !aligned16(A) || !aligned16(B)) { set_error("gspl_spotless_mask_fwd", "G, A and B must be aligned to 16 bytes"); return GSPL_ERR_INVALID_ARG; }
     const int OH = H ? H : mh, OW = W ? W : mw;
     const dim3 grid((OW + 63) / 64, (OH + SLS_BLOCK / 64 - 1) / (SLS_BLOCK / 64));
     if (H) hipLaunchKernelGGL(sls_fwd_kernel<true>, grid, dim3(SLS_BLOCK), 0, (hipStream_t)stream, p, G, A, B, w2, b2, out);
@@ -452,7 +432,7 @@ extern "C" int gspl_spotless_mask_bwd(int h0, int w0, int mh, int mw, int H, int
     SlsShape p;
     if (const int rc = sls_shape("gspl_spotless_mask_bwd", h0, w0, mh, mw, H, W, p)) return rc;
     if (!G || !A || !B || !w2 || !b2 || !v_out || !v_G || !v_A || !v_B || !v_w || !workspace) return fail_arg("gspl_spotless_mask_bwd");
-    if (!sls_aligned(G) || !sls_aligned(A) || !sls_aligned(B) || !sls_aligned(workspace)) {
+    if (!aligned16(G) || !aligned16(A) || !aligned16(B) || !aligned16(workspace)) {
         set_error("gspl_spotless_mask_bwd", "G, A, B and the workspace must be aligned to 16 bytes");
         return GSPL_ERR_INVALID_ARG;
     }
