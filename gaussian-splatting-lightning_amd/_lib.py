@@ -27,7 +27,7 @@ class HipLibraryError(RuntimeError):
 # The binding is READ from the header when this module is imported: entry points, constants and structs are written down once, in
 # include/gspl_hip.h.  The parser knows exactly the C the header uses; whatever it cannot classify raises.
 _SCALARS = {"int": c_int, "float": c_float, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64,
-            "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "uint8_t": ctypes.c_uint8, "uint16_t": ctypes.c_uint16}
+            "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "uint8_t": ctypes.c_uint8, "uint16_t": ctypes.c_uint16, "int8_t": ctypes.c_int8}
 _RETURNS = {"int": c_int, "size_t": ctypes.c_size_t, "void*": c_void_p, "const char*": ctypes.c_char_p}
 _DECLARATION = re.compile(r"(?:const\s+)?(\w+)(\s+|\s*(?:\*\s*(?:const\b\s*)?)+)(\w+)")
 

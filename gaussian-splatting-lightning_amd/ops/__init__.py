@@ -45,6 +45,9 @@ reference's renderers call (same names, argument meaning and error behaviour):
   The Glossy-Gaussian route's view-dependent opacity (internal/renderers/glossy_renderer.py `get_opacities`,
   internal/models/glossy_gaussian.py `get_view_dep_opacities`: F.normalize + `eval_sh_decomposed` + clamp in torch ops)
       sh_view_opacities, and the launches alone: sh_view_opacities_forward / sh_view_opacities_backward
+  The partition-LoD route's per-frame front (internal/renderers/partition_lod_renderer.py:550-625: distances, thresholds, the frustum
+  test, and the concatenation of the chosen levels; the module-level API is gspl_amd.lod)
+      lod_select, lod_gather
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -87,6 +90,7 @@ from .spotless import (spotless_mask, spotless_mask_forward, spotless_mask_backw
 from .segany import (segany_mask_stats, segany_pack_membership, segany_pair_labels, segany_correspondence_loss, segany_loss_forward,
                      segany_loss_backward, SeganyLossState, _SeganyLossFn)
 from .glossy import sh_view_opacities, sh_view_opacities_forward, sh_view_opacities_backward, _ShOpacityFn
+from .lod import lod_select, lod_gather
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

@@ -25,3 +25,4 @@ from .hip_swag_renderer import HipSWAGRenderer  # noqa: F401,E402
 from .hip_gsplat_appearance_embedding_renderer import HipGSplatAppearanceEmbeddingRenderer, HipGSplatAppearanceEmbeddingRendererModule  # noqa: F401,E402
 from .hip_vanilla_gs4d_renderer import HipVanillaGS4DRenderer  # noqa: F401,E402
 from .hip_glossy_renderer import HipGlossyRenderer, HipGlossyRendererModule  # noqa: F401,E402
+from .hip_partition_lod_renderer import HipPartitionLoDRenderer, HipPartitionLoDRendererModule  # noqa: F401,E402

@@ -1350,6 +1350,54 @@ int gspl_sh_opacity_fwd(int N, int degree, int n_rest, const float* means, const
 int gspl_sh_opacity_bwd(int N, int degree, int n_rest, const float* means, const float* origin, const float* dc, const float* rest,
                         const float* v_opacities, float* v_dc, float* v_rest, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 26. The per-frame front of the partition-LoD route (csrc/lod.hip).  PURELY ADDITIVE: two new entry points and three constants, no
+ *    new struct, nothing existing changes, GSPL_ABI_VERSION stays 39.  What `PartitionLoDRendererModule.forward`
+ *    (internal/renderers/partition_lod_renderer.py:550-625) does in front of the rasterizer: one level of detail per partition from the
+ *    camera's distance, an optional frustum test, and the concatenation of the chosen models' property arrays.  The distance and the
+ *    level rule are torch code there and are pinned directly (tests/lod_oracle.py against tests/golden/ref_lod.npz); the frustum test
+ *    is pytorch3d's box overlap there and an exact separating-axis test here: parity with pytorch3d's build is UNPINNED, the two
+ *    criteria differ for solids that touch.  fp32 data, device pointers only, no float atomics: two runs give the same bits.
+ *
+ *  The table: L levels x P partitions of Gaussians, every property one flat array over all segments; segment (level l, partition p)
+ *  is rows seg_start[l P + p] .. seg_start[l P + p + 1] of each (seg_start [L P + 1] int64, rising).  1 <= P <= 65536, 1 <= L <= 127.
+ *
+ *  gspl_lod_select: ONE launch of one workgroup.  camera_center [3], transform [3, 3] (the orientation transform, row-major),
+ *      box_min / box_max [P, 2], thresholds [L - 1] (NULL if and only if L == 1), prev_lod [P] int8 and prev_visible [P] u8 (the
+ *      previous frame's; 127 in prev_lod marks "none yet").  Read with visibility_filter != 0 only (NULL allowed otherwise):
+ *      boxes3d [P, 8, 3] world-space corners, one face clockwise and then the opposite face, corner i + 4 across an edge from
+ *      corner i; world_to_camera [4, 4] as the reference keeps it (transposed: x_cam = x_world @ M[:3, :3] + M[3, :3]);
+ *      K [3, 3] the intrinsics matrix; width, height.  Written:
+ *      distance [P] = sqrt(sum(max(max(box_min - p, p - box_max), 0)^2)),  p = (camera_center @ transform)[:2], each operation rounded
+ *        on its own, in the reference's order;
+ *      lod [P] int8 = the smallest i with distance < thresholds[i], else L - 1;
+ *      visible [P] u8 = 1 without the filter.  With it: the frustum has the image corners (0, 0), (W, 0), (W, H), (0, H) through
+ *        K^-1 at depth 0.1 and at depth 10 max(distance); a partition is visible when NO axis among the 6 + 6 face normals (the cross
+ *        product of a face's diagonals) and the 6 x 6 cross products of edge directions (two edges of the first face and the four
+ *        edges between the faces, of either solid) separates its box, taken to camera space, from the frustum with a gap >= 0.  An
+ *        axis a x b with |a x b|^2 <= 1e-12 |a|^2 |b|^2 is skipped.  The partition with the smallest distance (the lowest index
+ *        among equals) is always visible.
+ *      dst_start [P + 1] int64 = the exclusive scan of the chosen segments' lengths, an invisible partition counting 0 rows;
+ *      record [2] int64 = { dst_start[P], changed }: changed = 1 when lod or visible differs from prev_lod / prev_visible anywhere.
+ *      lod / visible may not alias prev_lod / prev_visible.
+ *  gspl_lod_gather: ONE launch for the five arrays means [R, 3], shs [R, K, 3], opacities [R, 1], scales [R, 3], rotations [R, 4]
+ *      (R = seg_start[L P], 1 <= K <= 64) -> the first n = dst_start[P] rows of out_*: rows dst_start[p] .. dst_start[p + 1] are the
+ *      rows of segment (lod[p], p), in partition order.  Rows from n on are not touched.  All offsets are 64-bit (csrc/gspl_lod_index.h,
+ *      built by the host compiler too).  A segment that does not lie inside 0 .. R, or a level outside 0 .. L - 1, copies nothing; no
+ *      address outside the first n rows of an out_* array is ever written.  n == 0 succeeds without a launch.  Bit-exact copies.
+ *  Anything else (P, L, K out of range, n > R, a NULL required pointer): GSPL_ERR_INVALID_ARG, nothing is launched.
+ * ---------------------------------------------------------------------------------------- */
+#define GSPL_LOD_MAX_PARTITIONS 65536
+#define GSPL_LOD_MAX_LEVELS 127
+#define GSPL_LOD_MAX_COEFFS 64
+int gspl_lod_select(int P, int L, const float* camera_center, const float* transform, const float* box_min, const float* box_max,
+                    const float* thresholds, const float* boxes3d, const float* world_to_camera, const float* K, int width, int height,
+                    int visibility_filter, const int64_t* seg_start, const int8_t* prev_lod, const uint8_t* prev_visible,
+                    float* distance, int8_t* lod, uint8_t* visible, int64_t* dst_start, int64_t* record, void* stream);
+int gspl_lod_gather(int P, int L, int K, int64_t R, int64_t n, const int64_t* seg_start, const int8_t* lod, const int64_t* dst_start,
+                    const float* means, const float* shs, const float* opacities, const float* scales, const float* rotations,
+                    float* out_means, float* out_shs, float* out_opacities, float* out_scales, float* out_rotations, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
