@@ -53,8 +53,9 @@ Host side only: shape checks, buffer allocation through torch's caching allocato
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
 
 One module per concern: projection (+ SH colours), binning, compositing, inria (the fused rasterizer), sharded (records and the
-three-node step of the Gaussian-sharded renderer), side (radix sort wrappers, distCUDA2, the photometric loss); `_common` holds the
-shared helpers and `_state.STATE` every piece of mutable run-time state.  This package re-exports all of them under the names the
+three-node step of the Gaussian-sharded renderer), side (radix sort wrappers, distCUDA2, the photometric loss), and one per route; `_common` holds the
+streams and the parameter updates in flight, `_args` the argument checks the route ops share, and `_state.STATE` every piece of
+mutable run-time state.  This package re-exports all of them under the names the
 single-file version had, including the module-level switches (ops.FUSED_INRIA = False still works: they are properties that read
 and write STATE).
 """

@@ -9,6 +9,7 @@ import torch
 from torch import Tensor
 
 from .. import _lib as L
+from ._args import raw_ptr as _raw_ptr      # (re-exported: the rasterizer ops take it from here)
 from ._state import STATE as S
 
 _SUPPORTED_D = (1, 2, 3, 4, 8)
@@ -66,12 +67,6 @@ def _rows(g: Optional[Tensor], width: int):
         if len(lead) == 1 and g.stride(lead[0]) >= width:
             return g, g.stride(lead[0])
     return g.contiguous(), 0
-
-
-def _raw_ptr(t: Optional[Tensor]):
-    """Device pointer of a possibly non-contiguous tensor's first element."""
-    import ctypes
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def _grad_or_zeros(g: Optional[Tensor], like_shape, device) -> Tensor:

@@ -21,6 +21,7 @@ import torch
 from torch import Tensor
 
 from .. import _lib as L
+from . import _args as A
 from ._common import _guarded
 
 ROW_TILE = 32            # AP_TILE: rows of one wave tile (the MFMA's N)
@@ -108,10 +109,7 @@ def appearance_mlp_forward(features: Tensor, weights, biases, embedding: Tensor,
                            output_activation: str = "sigmoid", out: Optional[Tensor] = None) -> Tensor:
     """The forward launch alone: contiguous float32 tensors on the GPU, mask uint8 -> out [N, n_out], every row written."""
     net = _Net(features, weights, biases, embedding, mask, means, camera_center, n_view_frequencies, normalize, output_activation)
-    if out is None:
-        out = torch.empty((net.N, net.n_out), dtype=torch.float32, device=features.device)
-    elif tuple(out.shape) != (net.N, net.n_out) or out.dtype != torch.float32 or out.device != features.device:
-        raise ValueError(f"appearance_mlp_forward: out must be float32 [{net.N}, {net.n_out}] on {features.device}")
+    out = A.out("appearance_mlp_forward", "out", out, (net.N, net.n_out), torch.float32, features, contiguous=False)
     L.call("gspl_appearance_mlp_fwd", *net.head(), L.ptr(out), L.stream())
     return out
 
@@ -125,8 +123,7 @@ def appearance_mlp_backward(features: Tensor, weights, biases, embedding: Tensor
     [W_0 | b_0 | W_1 | b_1 | ... | embedding]; every element of both is written (masked rows of v_features as zeros).  `v_features`
     and `v_params` may be the caller's buffers.  want_params=False: no weight-gradient arithmetic and no reduce."""
     net = _Net(features, weights, biases, embedding, mask, means, camera_center, n_view_frequencies, normalize, output_activation)
-    if tuple(v_out.shape) != (net.N, net.n_out):
-        raise ValueError(f"appearance_mlp_backward: v_out must be [{net.N}, {net.n_out}], got {tuple(v_out.shape)}")
+    A.shape("appearance_mlp_backward", "v_out", v_out, (net.N, net.n_out))
     v = v_out.to(torch.float32).contiguous()
     dev = features.device
     if want_features and v_features is None:
@@ -205,9 +202,11 @@ def appearance_mlp(features: Tensor, weights: Sequence[Tensor], biases: Sequence
     summed in a fixed order (no float atomics): two backward calls give the same bits.  Parameters that need no gradient cost no
     weight-gradient arithmetic.  Non-contiguous inputs are copied.  What is not built raises NotImplementedError naming the option
     before any launch; CPU tensors raise RuntimeError: there is no fallback here."""
-    weights, biases = list(weights), list(biases)
-    if not isinstance(features, Tensor) or not isinstance(embedding, Tensor) or not all(isinstance(t, Tensor) for t in weights + biases):
-        raise TypeError("appearance_mlp: features, embedding, weights and biases must be tensors")
+    who, weights, biases = "appearance_mlp", list(weights), list(biases)
+    named = ([("features", features), ("embedding", embedding)] + [(f"weights[{i}]", w) for i, w in enumerate(weights)]
+             + [(f"biases[{i}]", b) for i, b in enumerate(biases)])
+    for name, t in named:
+        A.tensor(who, name, t)
     if features.dim() != 2:
         raise ValueError(f"appearance_mlp: features must be [N, F], got {tuple(features.shape)}")
     if len(weights) != len(biases) or not weights:
@@ -228,11 +227,8 @@ def appearance_mlp(features: Tensor, weights: Sequence[Tensor], biases: Sequence
             raise ValueError(f"appearance_mlp: weights[{layer}] must be {list(want)}, got {list(w.shape)}")
         if b.shape[0] != want[0]:
             raise ValueError(f"appearance_mlp: biases[{layer}] must be [{want[0]}], got {list(b.shape)}")
-    tensors = [features, embedding] + weights + biases
-    if not features.is_cuda:
-        raise RuntimeError("appearance_mlp: features must be on the GPU; there is no CPU fallback")
-    if any(t.device != features.device for t in tensors):
-        raise RuntimeError(f"appearance_mlp: every tensor must be on {features.device}")
+    for name, t in named:
+        A.on_gpu(who, name, t, features, "features")
     if N >= 2 ** 31 - ROWS_PER_PASS:
         raise ValueError(f"appearance_mlp: features has {N} rows; fewer than 2^31 - {ROWS_PER_PASS} are built")
     if mask is not None:
@@ -244,8 +240,8 @@ def appearance_mlp(features: Tensor, weights: Sequence[Tensor], biases: Sequence
             raise ValueError("appearance_mlp: n_view_frequencies > 0 needs means and camera_center")
         if tuple(means.shape) != (N, 3) or camera_center.numel() != 3:
             raise ValueError(f"appearance_mlp: means must be [{N}, 3] and camera_center [3]")
-        if not means.is_cuda or not camera_center.is_cuda:
-            raise RuntimeError("appearance_mlp: means and camera_center must be on the GPU (camera_center stays on the device)")
+        A.on_gpu(who, "means", means)
+        A.on_gpu(who, "camera_center", camera_center)      # (it stays on the device)
         means = means.detach().to(torch.float32).contiguous()
         camera_center = camera_center.detach().to(torch.float32).reshape(3).contiguous()
     else:

@@ -11,28 +11,16 @@ per direction each (include/gspl_hip.h section 14, csrc/bilagrid.hip).
 GPU only, float32; no fallback."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
 from torch import Tensor
 from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
+from . import _args as A
+from ._args import raw_ptr as _addr
 from ._common import _guarded
 
 HWC, CHW = L.GSPL_LAYOUT_HWC, L.GSPL_LAYOUT_CHW
-
-
-def _addr(t: Tensor):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _gpu_f32(t: Tensor, name: str) -> Tensor:
-    if not isinstance(t, Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{name}: the bilateral-grid ops run on the GPU only; there is no CPU fallback")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name}: float32 is needed, got {t.dtype}")
-    return t
 
 
 def _image_layout(t: Tensor):
@@ -54,8 +42,7 @@ def _empty_image(B: int, H: int, W: int, layout: int, device) -> Tensor:
 def _grid_shape(grids: Tensor):
     if grids.dim() != 5 or grids.shape[1] != 12:
         raise ValueError(f"grids must be [N, 12, L, H, W], got {tuple(grids.shape)}")
-    if not grids.is_contiguous():
-        raise RuntimeError("grids: a contiguous tensor is needed")
+    A.contiguous(None, "grids", grids)
     N, _, Lz, GH, GW = (int(s) for s in grids.shape)
     return N, Lz, GH, GW
 
@@ -99,9 +86,8 @@ class _SliceFn(torch.autograd.Function):
 
 def bilagrid_slice(grids: Tensor, xy: Tensor, rgb: Tensor, grid_idx: Tensor) -> Tensor:
     """The affine-transformed colours [B, H, W, 3] (header section 14); gradients reach `grids` and `rgb`, never `xy`."""
-    _gpu_f32(grids, "grids")
-    _gpu_f32(xy, "xy")
-    _gpu_f32(rgb, "rgb")
+    for name, t in (("grids", grids), ("xy", xy), ("rgb", rgb)):
+        A.gpu_f32("bilateral-grid", name, t)
     if rgb.dim() != 4 or rgb.shape[-1] != 3:
         raise ValueError(f"rgb must be [B, H, W, 3], got {tuple(rgb.shape)}")
     B, H, W, _ = (int(s) for s in rgb.shape)
@@ -149,9 +135,8 @@ class _TvFn(torch.autograd.Function):
 
 def bilagrid_tv(x: Tensor) -> Tensor:
     """TV = (1/N) sum_d S_d / K_d of x [N, C, n1, n2, n3] (header section 14), a 0-d tensor with a gradient to x."""
-    _gpu_f32(x, "x")
+    A.gpu_f32("bilateral-grid", "x", x)
     if x.dim() != 5 or x.numel() == 0:
         raise ValueError(f"x must be a non-empty 5-D tensor [N, C, n1, n2, n3], got {tuple(x.shape)}")
-    if not x.is_contiguous():
-        raise RuntimeError("x: a contiguous tensor is needed")
+    A.contiguous(None, "x", x)
     return _TvFn.apply(x)

@@ -22,18 +22,12 @@ from torch import Tensor
 from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
+from . import _args as A
 from ._common import _guarded, _f32c
 
 
-def _gpu(t, name: str) -> Tensor:
-    if not isinstance(t, Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{name}: the environment-light ops run on the GPU only; there is no CPU fallback")
-    return t
-
-
 def _texture(base: Tensor) -> Tensor:
-    if not isinstance(base, Tensor):
-        raise TypeError("the texture must be a tensor")
+    A.tensor(None, "the texture", base)
     if base.dim() == 5 and base.shape[0] == 1:
         base = base[0]
     if base.dim() != 4 or base.shape[0] != 6 or base.shape[1] != base.shape[2] or base.shape[1] < 1:
@@ -74,10 +68,8 @@ def cubemap_sample(base: Tensor, dirs: Tensor, filter_mode: str = "linear", boun
         raise ValueError(f"the directions must be [..., 3], got {list(getattr(dirs, 'shape', ()))}")
     if dirs.requires_grad:
         raise NotImplementedError("there is no gradient for the directions: detach them")
-    _gpu(base, "base")
-    _gpu(dirs, "dirs")
-    if dirs.device != base.device:
-        raise RuntimeError(f"the directions must be on the texture's device ({base.device}), got {dirs.device}")
+    A.on_gpu(None, "base", base, family="environment-light")
+    A.on_gpu(None, "dirs", dirs, base, "base", family="environment-light")
     out = _CubemapFn.apply(_f32c(base), _f32c(dirs.reshape(-1, 3)))
     return out.view(*dirs.shape[:-1], 3)
 
@@ -131,7 +123,7 @@ def envlight_blend(rgb: Tensor, alpha: Tensor, base: Tensor, c2w_rotation: Tenso
     float32 directions [H, W, 3] the kernel sampled along."""
     base = _texture(base)
     for t, name in ((rgb, "rgb"), (alpha, "alpha"), (base, "base"), (c2w_rotation, "c2w_rotation")):
-        _gpu(t, name)
+        A.on_gpu(None, name, t, family="environment-light")
     if rgb.dim() != 3 or rgb.shape[0] != 3:
         raise ValueError(f"rgb must be [3, H, W], got {list(rgb.shape)}")
     H, W = int(rgb.shape[1]), int(rgb.shape[2])
@@ -140,7 +132,7 @@ def envlight_blend(rgb: Tensor, alpha: Tensor, base: Tensor, c2w_rotation: Tenso
     if tuple(c2w_rotation.shape) != (3, 3):
         raise ValueError(f"c2w_rotation must be [3, 3], got {list(c2w_rotation.shape)}")
     if jitter is not None:
-        _gpu(jitter, "jitter")
+        A.on_gpu(None, "jitter", jitter, family="environment-light")
         if tuple(jitter.shape) != (2, H, W):
             raise ValueError(f"jitter must be [2, {H}, {W}], got {list(jitter.shape)}")
         jitter = _f32c(jitter.detach())

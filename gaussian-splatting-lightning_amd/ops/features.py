@@ -8,6 +8,7 @@ import torch
 from torch import Tensor
 
 from .. import _lib as L
+from . import _args as A
 from ._common import _guarded, _f32c, _grad_or_zeros
 from .binning import LazyLists, bin_gaussians
 from .compositing import _composite
@@ -93,8 +94,8 @@ def rasterize_features(xys: Tensor, depths: Tensor, radii: Tensor, conics: Tenso
         raise NotImplementedError("block_width must be 8, 16 or 32 (the reference default is 16, gsplat_renderer.py:6)")
     if features.dim() != 2 or features.shape[0] != xys.shape[0] or features.shape[1] < 1:
         raise ValueError(f"features must be [N, D] with D >= 1 (got {tuple(features.shape)} for {xys.shape[0]} splats)")
-    if not (xys.is_cuda and features.is_cuda):
-        raise RuntimeError("gspl ops run on the GPU only (tensor is on %s); there is no CPU fallback" % (features if xys.is_cuda else xys).device)
+    A.on_gpu(None, "xys", xys, family="gspl")
+    A.on_gpu(None, "features", features, family="gspl")
     flat, offsets = isects if isects is not None else bin_gaussians(xys, depths, radii, img_height, img_width, block_width,
                                                                     conics=conics, opacities=opacity, lazy=True)
     layout = L.GSPL_LAYOUT_CHW if channels_first else L.GSPL_LAYOUT_HWC

@@ -10,28 +10,30 @@ GPU only, float32; no fallback.  The reference's arithmetic is torch code: the f
 through tests/golden/ref_glossy.npz, and the kernels to the oracle."""
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Tuple
 
 import torch
 from torch import Tensor
 
 from .. import _lib as L
+from . import _args as A
 from ._common import _guarded, _f32c, _await_updates
 
 MAX_REST = 61          # columns of opacity_rest the kernels stage (the reference's widest row, degree 4, has 24)
 
 
 def _check(who: str, degree, means, camera_center, dc, rest) -> Tuple[int, int, int]:
-    """Every refusal of the op, in an order that lets a machine without a GPU meet all of them: types, shapes and the degree
-    (ValueError), the dtype (NotImplementedError), the device (RuntimeError) -> degree, N, Kr."""
-    for name, t in (("means", means), ("camera_center", camera_center), ("opacity_dc", dc), ("opacity_rest", rest)):
+    """Every refusal of the op, in `_args`' order for a machine without a GPU: types, shapes and the degree, the dtype, the
+    device -> degree, N, Kr.  This runs twice a frame, so each test stands here and `_args` is entered only to refuse."""
+    named = (("means", means), ("camera_center", camera_center), ("opacity_dc", dc), ("opacity_rest", rest))
+    for name, t in named:
         if not isinstance(t, Tensor):
-            raise TypeError(f"{who}: {name} must be a tensor")
+            A.tensor(who, name, t)
     if means.dim() != 2 or means.shape[1] != 3:
-        raise ValueError(f"{who}: means must be [N, 3], got {tuple(means.shape)}")
+        A.shape(who, "means", means, ("N", 3))
     N = means.shape[0]
     if camera_center.numel() != 3:
-        raise ValueError(f"{who}: camera_center must hold 3 values, got {tuple(camera_center.shape)}")
+        A.numel(who, "camera_center", camera_center, 3)
     if tuple(dc.shape) not in ((N, 1, 1), (N, 1), (N,)):
         raise ValueError(f"{who}: opacity_dc must be [{N}, 1, 1], [{N}, 1] or [{N}], got {tuple(dc.shape)}")
     if rest.dim() not in (2, 3) or rest.shape[0] != N or (rest.dim() == 3 and rest.shape[2] != 1):
@@ -44,23 +46,13 @@ def _check(who: str, degree, means, camera_center, dc, rest) -> Tuple[int, int, 
         raise ValueError(f"{who}: degree {degree} needs {(degree + 1) ** 2 - 1} columns of opacity_rest, got {Kr}")
     if Kr > MAX_REST:
         raise NotImplementedError(f"{who}: up to {MAX_REST} columns of opacity_rest are built, got {Kr}")
-    for name, t in (("means", means), ("camera_center", camera_center), ("opacity_dc", dc), ("opacity_rest", rest)):
+    for name, t in named:
         if t.dtype != torch.float32:
-            raise NotImplementedError(f"{who}: {name} must be float32 (the only dtype built), got {t.dtype}")
-    for name, t in (("means", means), ("camera_center", camera_center), ("opacity_dc", dc), ("opacity_rest", rest)):
-        if not t.is_cuda:
-            raise RuntimeError(f"{who}: {name} must be on the GPU; there is no CPU fallback")
-        if t.device != means.device:
-            raise RuntimeError(f"{who}: {name} is on {t.device}, means on {means.device}")
+            A.dtype(who, name, t, torch.float32)
+    for name, t in named:
+        if not t.is_cuda or t.device != means.device:
+            A.on_gpu(who, name, t, means, "means")
     return degree, N, Kr
-
-
-def _buffer(who: str, name: str, t: Optional[Tensor], shape, like: Tensor) -> Tensor:
-    if t is None:
-        return torch.empty(shape, dtype=torch.float32, device=like.device)
-    if not isinstance(t, Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or t.device != like.device or not t.is_contiguous():
-        raise ValueError(f"{who}: {name} must be contiguous float32 {tuple(shape)} on {like.device}")
-    return t
 
 
 def _operands(degree, means, camera_center, dc, rest, who):
@@ -76,7 +68,7 @@ def sh_view_opacities_forward(degree: int, means: Tensor, camera_center: Tensor,
     """The forward launch alone, outside autograd -> opacities [N] (written into `out` when one is given: contiguous float32 [N])."""
     who = "sh_view_opacities_forward"
     degree, N, Kr, means, origin, dc, rest = _operands(degree, means, camera_center, opacity_dc, opacity_rest, who)
-    out = _buffer(who, "out", out, (N,), means)
+    out = A.out(who, "out", out, (N,), torch.float32, means)
     _await_updates(opacity_dc, opacity_rest)
     L.call("gspl_sh_opacity_fwd", N, degree, Kr, L.ptr(means), L.ptr(origin), L.ptr(dc), L.ptr(rest) if Kr else None,
            L.ptr(out), L.stream())
@@ -93,8 +85,8 @@ def sh_view_opacities_backward(degree: int, means: Tensor, camera_center: Tensor
     if not isinstance(v_opacities, Tensor) or v_opacities.numel() != N or v_opacities.device != means.device:
         raise ValueError(f"{who}: v_opacities must hold {N} values on {means.device}")
     v = _f32c(v_opacities.detach().reshape(N))
-    v_dc = _buffer(who, "v_dc", v_dc, (N,), means)
-    v_rest = _buffer(who, "v_rest", v_rest, (N, Kr), means)
+    v_dc = A.out(who, "v_dc", v_dc, (N,), torch.float32, means)
+    v_rest = A.out(who, "v_rest", v_rest, (N, Kr), torch.float32, means)
     _await_updates(opacity_dc, opacity_rest)
     L.call("gspl_sh_opacity_bwd", N, degree, Kr, L.ptr(means), L.ptr(origin), L.ptr(dc), L.ptr(rest) if Kr else None,
            L.ptr(v), L.ptr(v_dc), L.ptr(v_rest) if Kr else None, L.stream())

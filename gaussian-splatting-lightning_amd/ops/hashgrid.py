@@ -12,7 +12,6 @@ GPU only, float32; no fallback.  Parity with tiny-cuda-nn's own build is UNPINNE
 published rules, checked against the fp64 oracle tests/hashgrid_oracle.py."""
 from __future__ import annotations
 
-import ctypes
 import math
 from dataclasses import dataclass
 
@@ -21,6 +20,8 @@ import torch
 from torch import Tensor
 
 from .. import _lib as L
+from . import _args as A
+from ._args import host_ptr as _host
 from ._common import _guarded
 
 MAX_LEVELS = 32
@@ -104,10 +105,6 @@ def hashgrid_table(levels: HashGridLevels, seed: int = 1337, device=None) -> Ten
     return table if device is None else table.to(device)
 
 
-def _host(a: np.ndarray):
-    return ctypes.c_void_p(a.ctypes.data)
-
-
 @_guarded(0)
 def hashgrid_forward(x: Tensor, table: Tensor, levels: HashGridLevels, out: Tensor = None) -> Tensor:
     """The forward launch alone, outside autograd: x [N, D] and table contiguous float32 on the GPU -> out [N, L * F] (written into
@@ -115,8 +112,8 @@ def hashgrid_forward(x: Tensor, table: Tensor, levels: HashGridLevels, out: Tens
     lv, N = levels, x.shape[0]
     if out is None:
         out = torch.empty((N, lv.n_output_dims), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (N, lv.n_output_dims) or out.dtype != torch.float32 or out.device != x.device:
-        raise ValueError(f"hashgrid_forward: out must be float32 [{N}, {lv.n_output_dims}] on {x.device}, got {out.dtype} {tuple(out.shape)}")
+    else:
+        A.buffer("hashgrid_forward", "out", out, (N, lv.n_output_dims), torch.float32, x, contiguous=False)
     L.call("gspl_hashgrid_fwd", N, lv.n_input_dims, lv.n_features_per_level, lv.n_levels, _host(lv.scales), _host(lv.resolutions),
            _host(lv.offsets), L.ptr(x, torch.float32), L.ptr(table, torch.float32), L.ptr(out), L.stream())
     return out
@@ -127,13 +124,10 @@ def hashgrid_backward(x: Tensor, table: Tensor, levels: HashGridLevels, v_out: T
     """The backward launches alone: v_out [N, L * F] -> (v_table, v_x).  `v_table` (the table's shape, contiguous float32) is
     ACCUMULATED into — pass a cleared buffer, or a gradient to add to; None: not computed.  v_x [N, D] is computed when `want_x`."""
     lv, N = levels, x.shape[0]
-    if tuple(v_out.shape) != (N, lv.n_output_dims):
-        raise ValueError(f"hashgrid_backward: v_out must be [{N}, {lv.n_output_dims}], got {tuple(v_out.shape)}")
-    if v_table is not None and (v_table.numel() != lv.n_params or v_table.dtype != torch.float32 or v_table.device != x.device):
-        raise ValueError(f"hashgrid_backward: v_table must hold {lv.n_params} float32 on {x.device}, got {v_table.dtype} {tuple(v_table.shape)}")
-    v = v_out.to(torch.float32).contiguous()
-    if v.data_ptr() % 16:
-        v = v.clone()
+    A.shape("hashgrid_backward", "v_out", v_out, (N, lv.n_output_dims))
+    if v_table is not None:
+        A.buffer("hashgrid_backward", "v_table", v_table, lv.n_params, torch.float32, x, contiguous=False)
+    v = A.rows16(v_out)
     v_x = torch.empty_like(x) if want_x else None
     if v_table is not None or want_x:
         L.call("gspl_hashgrid_bwd", N, lv.n_input_dims, lv.n_features_per_level, lv.n_levels, _host(lv.scales), _host(lv.resolutions),
@@ -166,23 +160,23 @@ def hashgrid_encode(x: Tensor, table: Tensor, levels: HashGridLevels) -> Tensor:
     is refused.  CPU tensors raise RuntimeError: there is no fallback."""
     if not isinstance(levels, HashGridLevels):
         raise TypeError("hashgrid_encode: levels must come from ops.hashgrid_levels")
+    who = "hashgrid_encode"      # (a per-frame call: each test stands here, and `_args` is entered only to refuse)
     if not isinstance(x, Tensor) or not isinstance(table, Tensor):
-        raise TypeError("hashgrid_encode: x and table must be tensors")
-    if not x.is_cuda:
-        raise RuntimeError("hashgrid_encode: x must be on the GPU; there is no CPU fallback")
-    if not table.is_cuda or table.device != x.device:
-        raise RuntimeError(f"hashgrid_encode: table is on {table.device}, x on {x.device}")
-    if x.dtype != torch.float32:
-        raise RuntimeError(f"hashgrid_encode: x must be float32, got {x.dtype}")
-    if table.dtype != torch.float32:
-        raise RuntimeError(f"hashgrid_encode: table must be float32, got {table.dtype}")
+        A.tensor(who, "x", x)
+        A.tensor(who, "table", table)
+    if not x.is_cuda or not table.is_cuda or table.device != x.device:
+        A.on_gpu(who, "x", x)
+        A.on_gpu(who, "table", table, x, "x")
+    if x.dtype != torch.float32 or table.dtype != torch.float32:
+        A.dtype(who, "x", x, torch.float32, error=RuntimeError)
+        A.dtype(who, "table", table, torch.float32, error=RuntimeError)
     if x.dim() != 2 or x.shape[1] != levels.n_input_dims:
-        raise ValueError(f"hashgrid_encode: x must be [N, {levels.n_input_dims}], got {tuple(x.shape)}")
+        A.shape(who, "x", x, ("N", levels.n_input_dims))
     if tuple(table.shape) not in ((levels.n_params,), (levels.total, levels.n_features_per_level)):
         raise ValueError(f"hashgrid_encode: table must be [{levels.total}, {levels.n_features_per_level}] or flat [{levels.n_params}], "
                          f"got {tuple(table.shape)}")
     if x.shape[0] >= 2 ** 31:
         raise ValueError(f"hashgrid_encode: x has {x.shape[0]} rows; fewer than 2^31 are built")
-    if table.is_contiguous() and table.data_ptr() % 16:
-        raise ValueError("hashgrid_encode: table must be aligned to 16 bytes (a view into the middle of another tensor?)")
+    if table.data_ptr() % 16:
+        A.aligned16(who, "table", table)
     return _HashGridFn.apply(x, table, levels)

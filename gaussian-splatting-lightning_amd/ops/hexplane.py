@@ -12,7 +12,6 @@ GPU only, float32; no fallback.  The reference's arithmetic is torch code: the f
 through tests/golden/ref_hexplane.npz, and the kernels to the oracle."""
 from __future__ import annotations
 
-import ctypes
 import itertools
 from dataclasses import dataclass
 from typing import Sequence, Tuple, Union
@@ -22,6 +21,8 @@ import torch
 from torch import Tensor
 
 from .. import _lib as L
+from . import _args as A
+from ._args import host_ptr as _host
 from ._common import _guarded
 
 MAX_LEVELS = 8
@@ -114,10 +115,6 @@ def hexplane_box(aabb) -> np.ndarray:
     return np.ascontiguousarray(np.concatenate([aabb[0], scale]).astype(np.float32))
 
 
-def _host(a: np.ndarray):
-    return ctypes.c_void_p(a.ctypes.data)
-
-
 def _time(t, x: Tensor):
     """t -> (device pointer or None, the uniform value): a python number is ONE time for the call, a tensor [N] / [N, 1] one per point."""
     if isinstance(t, Tensor):
@@ -134,8 +131,8 @@ def hexplane_forward(x: Tensor, t: Union[float, Tensor], table: Tensor, box: np.
     lv, N = layout, x.shape[0]
     if out is None:
         out = torch.empty((N, lv.n_output_dims), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (N, lv.n_output_dims) or out.dtype != torch.float32 or out.device != x.device:
-        raise ValueError(f"hexplane_forward: out must be float32 [{N}, {lv.n_output_dims}] on {x.device}, got {out.dtype} {tuple(out.shape)}")
+    else:
+        A.buffer("hexplane_forward", "out", out, (N, lv.n_output_dims), torch.float32, x, contiguous=False)
     tp, tu = _time(t, x)
     L.call("gspl_hexplane_fwd", N, lv.n_features, lv.n_levels, _host(lv.resolutions), _host(lv.offsets), _host(box),
            L.ptr(x, torch.float32), L.ptr(tp), tu, L.ptr(table, torch.float32), L.ptr(out), L.stream())
@@ -149,15 +146,12 @@ def hexplane_backward(x: Tensor, t: Union[float, Tensor], table: Tensor, box: np
     ACCUMULATED into — pass a cleared buffer, or a gradient to add to; None: not computed.  v_x [N, 3] is computed when `want_x`, or
     written into the buffer `v_x` (contiguous float32 [N, 3]) when one is given."""
     lv, N = layout, x.shape[0]
-    if tuple(v_out.shape) != (N, lv.n_output_dims):
-        raise ValueError(f"hexplane_backward: v_out must be [{N}, {lv.n_output_dims}], got {tuple(v_out.shape)}")
-    if v_table is not None and (v_table.numel() != lv.n_params or v_table.dtype != torch.float32 or v_table.device != x.device):
-        raise ValueError(f"hexplane_backward: v_table must hold {lv.n_params} float32 on {x.device}, got {v_table.dtype} {tuple(v_table.shape)}")
-    v = v_out.to(torch.float32).contiguous()
-    if v.data_ptr() % 16:
-        v = v.clone()
-    if v_x is not None and (tuple(v_x.shape) != (N, 3) or v_x.dtype != torch.float32 or v_x.device != x.device):
-        raise ValueError(f"hexplane_backward: v_x must be float32 [{N}, 3] on {x.device}, got {v_x.dtype} {tuple(v_x.shape)}")
+    A.shape("hexplane_backward", "v_out", v_out, (N, lv.n_output_dims))
+    if v_table is not None:
+        A.buffer("hexplane_backward", "v_table", v_table, lv.n_params, torch.float32, x, contiguous=False)
+    v = A.rows16(v_out)
+    if v_x is not None:
+        A.buffer("hexplane_backward", "v_x", v_x, (N, 3), torch.float32, x, contiguous=False)
     if v_x is None and want_x:
         v_x = torch.empty_like(x)
     if v_table is not None or v_x is not None:
@@ -196,22 +190,22 @@ def hexplane_encode(x: Tensor, t: Union[float, Tensor], table: Tensor, aabb, lay
     x is copied; another dtype is refused.  CPU tensors raise RuntimeError: there is no fallback."""
     if not isinstance(layout, HexPlaneLayout):
         raise TypeError("hexplane_encode: layout must come from ops.hexplane_layout")
+    who = "hexplane_encode"      # (a per-frame call: each test stands here, and `_args` is entered only to refuse)
     if not isinstance(x, Tensor) or not isinstance(table, Tensor):
-        raise TypeError("hexplane_encode: x and table must be tensors")
-    if not x.is_cuda:
-        raise RuntimeError("hexplane_encode: x must be on the GPU; there is no CPU fallback")
-    if not table.is_cuda or table.device != x.device:
-        raise RuntimeError(f"hexplane_encode: table is on {table.device}, x on {x.device}")
-    if x.dtype != torch.float32:
-        raise NotImplementedError(f"hexplane_encode: x must be float32 (the only dtype built), got {x.dtype}")
-    if table.dtype != torch.float32:
-        raise NotImplementedError(f"hexplane_encode: table must be float32 (the only dtype built), got {table.dtype}")
+        A.tensor(who, "x", x)
+        A.tensor(who, "table", table)
+    if not x.is_cuda or not table.is_cuda or table.device != x.device:
+        A.on_gpu(who, "x", x)
+        A.on_gpu(who, "table", table, x, "x")
+    if x.dtype != torch.float32 or table.dtype != torch.float32:
+        A.dtype(who, "x", x, torch.float32)
+        A.dtype(who, "table", table, torch.float32)
     if x.dim() != 2 or x.shape[1] != 3:
-        raise ValueError(f"hexplane_encode: x must be [N, 3], got {tuple(x.shape)}")
+        A.shape(who, "x", x, ("N", 3))
     if tuple(table.shape) not in ((layout.n_params,), (layout.total, layout.n_features)):
         raise ValueError(f"hexplane_encode: table must be [{layout.total}, {layout.n_features}] or flat [{layout.n_params}], got {tuple(table.shape)}")
     if x.shape[0] >= 2 ** 31:
         raise NotImplementedError(f"hexplane_encode: N = {x.shape[0]} points; fewer than 2^31 are built")
-    if table.is_contiguous() and table.data_ptr() % 16:
-        raise ValueError("hexplane_encode: table must be aligned to 16 bytes (a view into the middle of another tensor?)")
+    if table.data_ptr() % 16:
+        A.aligned16(who, "table", table)
     return _HexPlaneFn.apply(x, table, t, hexplane_box(aabb), layout)

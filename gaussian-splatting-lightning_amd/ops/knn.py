@@ -18,6 +18,7 @@ import torch
 from torch import Tensor
 
 from .. import _lib as L
+from . import _args as A
 from ._common import _guarded
 
 MAX_K = 32
@@ -61,12 +62,10 @@ def knn_points(p1: Tensor, p2: Tensor, lengths1=None, lengths2=None, K: int = 1,
         raise ValueError(f"knn_points: K must be at least 1, got {K}")
     if K > MAX_K:
         raise NotImplementedError(f"knn_points: K <= {MAX_K} is built, got {K}")
-    if not p1.is_cuda or not p2.is_cuda:
-        raise RuntimeError("knn_points: the points must be on the GPU; there is no CPU fallback")
-    if p1.device != p2.device:
-        raise RuntimeError(f"knn_points: p1 is on {p1.device}, p2 on {p2.device}")
-    if p1.dtype != torch.float32 or p2.dtype != torch.float32:
-        raise RuntimeError(f"knn_points: float32 is needed, got {p1.dtype} / {p2.dtype}")
+    A.on_gpu("knn_points", "p1", p1)
+    A.on_gpu("knn_points", "p2", p2, p1, "p1")
+    A.dtype("knn_points", "p1", p1, torch.float32, error=RuntimeError)
+    A.dtype("knn_points", "p2", p2, torch.float32, error=RuntimeError)
     B, P1 = p1.shape[0], p1.shape[1]
     same = p1 is p2
     q = p1.detach().contiguous()
@@ -120,8 +119,7 @@ def knn_graph(idx: Tensor) -> KnnGraph:
     """idx [N, K] (any integer type, values 0 .. N-1, 1 <= K <= 32) -> KnnGraph.  Built on the device (count, scan, stable radix
     sort): the inverse lists are sorted by (i, k), so the structure is the same on every run.  The values are checked here, once
     (one read-back), because `smooth_features` trusts them."""
-    if not isinstance(idx, Tensor) or not idx.is_cuda:
-        raise RuntimeError("knn_graph: idx must be on the GPU; there is no CPU fallback")
+    A.on_gpu("knn_graph", "idx", idx)
     if idx.dim() != 2 or idx.dtype.is_floating_point or idx.dtype == torch.bool:
         raise ValueError(f"knn_graph: idx must be an integer tensor [N, K], got {tuple(idx.shape)} {idx.dtype}")
     N, K = idx.shape
@@ -183,14 +181,10 @@ def smooth_features(features: Tensor, graph: KnnGraph, columns=None) -> Tensor:
     nothing, a device tensor one read-back), None = all K.  Differentiable in `features`; the backward is bit-reproducible."""
     if not isinstance(graph, KnnGraph):
         raise TypeError("smooth_features: graph must come from ops.knn_graph")
-    if not isinstance(features, Tensor) or not features.is_cuda:
-        raise RuntimeError("smooth_features: features must be on the GPU; there is no CPU fallback")
-    if features.dtype != torch.float32:
-        raise RuntimeError(f"smooth_features: float32 is needed, got {features.dtype}")
+    A.dtype("smooth_features", "features", A.on_gpu("smooth_features", "features", features), torch.float32, error=RuntimeError)
     if features.dim() != 2 or features.shape[0] != graph.N:
         raise ValueError(f"smooth_features: features must be [{graph.N}, D], got {tuple(features.shape)}")
     if features.shape[1] < 1 or features.shape[1] > MAX_D:
         raise NotImplementedError(f"smooth_features: 1 <= D <= {MAX_D} is built, got {features.shape[1]}")
-    if features.device != graph.idx.device:
-        raise RuntimeError(f"smooth_features: features are on {features.device}, the graph on {graph.idx.device}")
+    A.on_gpu("smooth_features", "features", features, graph.idx, "the graph")
     return _SmoothFn.apply(features, graph, _column_mask(columns, graph.K))

@@ -17,6 +17,7 @@ import torch
 from torch import Tensor
 
 from .. import _lib as L
+from . import _args as A
 from ._common import _guarded
 
 MAX_PARTITIONS = L.GSPL_LOD_MAX_PARTITIONS      # one workgroup loops over them
@@ -29,39 +30,31 @@ def _widths(K: int):
     return {"means": (3,), "shs": (K, 3), "opacities": (1,), "scales": (3,), "rotations": (4,)}
 
 
-def _refuse(who: str, checks: Sequence[Tuple[str, object, Optional[tuple], torch.dtype]], anchor: Tensor):
-    """The refusals every tensor argument shares, in an order that lets a machine without a GPU meet all of them: types (TypeError),
-    shapes (ValueError), dtypes (NotImplementedError), devices and layout (RuntimeError).  A shape of None is checked by the caller."""
+def _check_all(who: str, checks: Sequence[Tuple[str, object, Optional[tuple], torch.dtype]], anchor: Tensor):
+    """(name, tensor, shape, dtype) each, pass by pass in `_args`' order for a machine without a GPU: types, shapes, dtypes, then
+    devices and layout.  A shape of None is checked by the caller.  This runs every frame over a dozen tensors, so each test stands
+    here and `_args` is entered only to refuse."""
     for name, t, _, _ in checks:
         if not isinstance(t, Tensor):
-            raise TypeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
+            A.tensor(who, name, t)
     for name, t, shape, _ in checks:
-        if shape is not None and tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{who}: {name} must be {list(shape)}, got {list(t.shape)}")
+        if shape is not None and tuple(t.shape) != shape:
+            A.shape(who, name, t, shape)
     for name, t, _, dtype in checks:
         if t.dtype != dtype:
-            raise NotImplementedError(f"{who}: {name} must be {str(dtype).replace('torch.', '')} (the only dtype built), got {t.dtype}")
+            A.dtype(who, name, t, dtype)
     for name, t, _, _ in checks:
-        if not t.is_cuda:
-            raise RuntimeError(f"{who}: {name} must be on the GPU; there is no CPU fallback")
-        if t.device != anchor.device:
-            raise RuntimeError(f"{who}: {name} is on {t.device}, the table on {anchor.device}")
+        if not t.is_cuda or t.device != anchor.device:
+            A.on_gpu(who, name, t, anchor, "the table")
         if not t.is_contiguous():
-            raise RuntimeError(f"{who}: {name} must be contiguous")
-
-
-def _out(who: str, name: str, t: Optional[Tensor], shape, dtype, like: Tensor) -> Tensor:
-    if t is None:
-        return torch.empty(shape, dtype=dtype, device=like.device)
-    if not isinstance(t, Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != like.device or not t.is_contiguous():
-        raise ValueError(f"{who}: {name} must be contiguous {str(dtype).replace('torch.', '')} {list(shape)} on {like.device}")
-    return t
+            A.contiguous(who, name, t)
 
 
 def _levels(who: str, seg_start, box_min) -> Tuple[int, int]:
     """-> (P, L) from box_min [P, 2] and seg_start [L P + 1]."""
     if not isinstance(seg_start, Tensor) or not isinstance(box_min, Tensor):
-        raise TypeError(f"{who}: seg_start and box_min must be tensors")
+        A.tensor(who, "seg_start", seg_start)
+        A.tensor(who, "box_min", box_min)
     if box_min.dim() != 2 or box_min.shape[1] != 2 or box_min.shape[0] < 1:
         raise ValueError(f"{who}: box_min must be [P, 2] with P >= 1, got {list(box_min.shape)}")
     P = box_min.shape[0]
@@ -98,14 +91,14 @@ def lod_select(seg_start: Tensor, camera_center: Tensor, transform: Tensor, box_
               ("prev_visible", prev_visible, (P,), torch.uint8)]
     if visibility_filter:
         checks += [("boxes3d", boxes3d, (P, 8, 3), f32), ("world_to_camera", world_to_camera, (4, 4), f32), ("Ks", Ks, (3, 3), f32)]
-    _refuse(who, checks, seg_start)
+    _check_all(who, checks, seg_start)
     if visibility_filter and (int(width) < 1 or int(height) < 1):
         raise ValueError(f"{who}: the visibility filter needs the image size, got {width} x {height}")
-    distance = _out(who, "distance", distance, (P,), f32, seg_start)
-    lod = _out(who, "lod", lod, (P,), torch.int8, seg_start)
-    visible = _out(who, "visible", visible, (P,), torch.uint8, seg_start)
-    dst_start = _out(who, "dst_start", dst_start, (P + 1,), torch.int64, seg_start)
-    record = _out(who, "record", record, (2,), torch.int64, seg_start)
+    distance = A.out(who, "distance", distance, (P,), f32, seg_start)
+    lod = A.out(who, "lod", lod, (P,), torch.int8, seg_start)
+    visible = A.out(who, "visible", visible, (P,), torch.uint8, seg_start)
+    dst_start = A.out(who, "dst_start", dst_start, (P + 1,), torch.int64, seg_start)
+    record = A.out(who, "record", record, (2,), torch.int64, seg_start)
     if lod.data_ptr() == prev_lod.data_ptr() or visible.data_ptr() == prev_visible.data_ptr():
         raise ValueError(f"{who}: lod / visible may not be the previous frame's arrays")
     on = bool(visibility_filter)
@@ -125,8 +118,7 @@ def lod_gather(seg_start: Tensor, lod: Tensor, dst_start: Tensor, n: int, means:
     buffers of at least n rows each, in the table's order; rows from n on are left as they are.  Bit-exact copies, one launch."""
     who = "lod_gather"
     for name, t in (("seg_start", seg_start), ("lod", lod), ("dst_start", dst_start), ("means", means), ("shs", shs)):
-        if not isinstance(t, Tensor):
-            raise TypeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
+        A.tensor(who, name, t)
     if lod.dim() != 1 or lod.numel() < 1:
         raise ValueError(f"{who}: lod must be [P], got {list(lod.shape)}")
     P = lod.numel()
@@ -153,12 +145,11 @@ def lod_gather(seg_start: Tensor, lod: Tensor, dst_start: Tensor, n: int, means:
         if len(out) != 5:
             raise ValueError(f"{who}: out must hold five buffers ({', '.join(PROPERTIES)})")
         for (name, w), t in zip(_widths(K).items(), out):
-            if not isinstance(t, Tensor):
-                raise TypeError(f"{who}: out {name} must be a tensor")
+            A.tensor(who, f"out {name}", t)
             if t.dim() != 1 + len(w) or tuple(t.shape[1:]) != w or t.shape[0] < n:
                 raise ValueError(f"{who}: out {name} must be [>= {n}, {', '.join(map(str, w))}], got {list(t.shape)}")
             checks.append((f"out {name}", t, None, f32))
-    _refuse(who, checks, seg_start)
+    _check_all(who, checks, seg_start)
     if out is None:
         out = [torch.empty((n,) + w, dtype=f32, device=seg_start.device) for w in _widths(K).values()]
     L.call("gspl_lod_gather", P, levels, K, R, n, L.ptr(seg_start), L.ptr(lod), L.ptr(dst_start), *[L.ptr(table[k]) for k in PROPERTIES],

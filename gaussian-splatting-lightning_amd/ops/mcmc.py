@@ -18,20 +18,16 @@ import torch
 from torch import Tensor
 
 from .. import _lib as L
+from . import _args as A
 from ._common import _guarded, join_pending_updates
 from ._state import STATE as S
 
 
-def _need(t: Tensor, name: str, numel: int) -> Tensor:
-    if not isinstance(t, Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{name}: the MCMC ops run on the GPU only; there is no CPU fallback")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name}: float32 is needed, got {t.dtype}")
-    if not t.is_contiguous():
-        raise RuntimeError(f"{name}: a contiguous tensor is needed")
-    if t.numel() != numel:
-        raise ValueError(f"{name}: {numel} elements expected, got {t.numel()} (shape {tuple(t.shape)})")
-    return t
+def _flat_rows(*rows):
+    """(name, tensor or None, elements) each: float32 on the GPU, contiguous, of that many elements whatever the shape."""
+    for name, t, n in rows:
+        if t is not None:
+            A.numel(None, name, A.contiguous(None, name, A.gpu_f32("MCMC", name, t)), n)
 
 
 @torch.no_grad()
@@ -39,18 +35,15 @@ def compute_relocation(opacities: Tensor, scales: Tensor, ratios: Tensor, binoms
     """new_opacities [M], new_scales [M,3] of Eq. 9 for each row with n = clamp(ratios, 1, n_max) copies (header section 13).
     opacities [M] and scales [M,3] are activated values; ratios of any integer dtype; binoms [n_max, n_max] (binoms[n,k] = C(n,k))."""
     M = opacities.shape[0] if opacities.dim() > 0 else 1
-    _need(opacities, "opacities", M)
-    _need(scales, "scales", 3 * M)
+    _flat_rows(("opacities", opacities, M), ("scales", scales, 3 * M))
     if not binoms.dim() == 2 or binoms.shape[0] != binoms.shape[1]:
         raise ValueError(f"binoms must be [n_max, n_max], got {tuple(binoms.shape)}")
     n_max = int(binoms.shape[0])
-    _need(binoms, "binoms", n_max * n_max)
-    if not isinstance(ratios, Tensor) or not ratios.is_cuda:
-        raise RuntimeError("ratios: the MCMC ops run on the GPU only; there is no CPU fallback")
+    _flat_rows(("binoms", binoms, n_max * n_max))
+    A.on_gpu(None, "ratios", ratios, family="MCMC")
     if ratios.dtype.is_floating_point or ratios.dtype == torch.bool or ratios.numel() != M:
         raise ValueError(f"ratios: {M} integers expected, got {ratios.numel()} of {ratios.dtype}")
-    if not ratios.is_contiguous():
-        raise RuntimeError("ratios: a contiguous tensor is needed")
+    A.contiguous(None, "ratios", ratios)
     if ratios.dtype != torch.int32:
         ratios = ratios.clamp(1, n_max).to(torch.int32)       # a new tensor: the caller's stays as it is
     new_opacities = torch.empty((M,), dtype=torch.float32, device=opacities.device)
@@ -95,12 +88,8 @@ def perturb_means_(means: Tensor, scales: Tensor, rotations: Tensor, opacities: 
     renderers.renderer.model_raw_parameters); raw=False: the activated getters' values.  noise_scale = noise_lr * the means' lr.
     eps [N,3] given in `noise`, or drawn inside the kernel from `generator` (default: the device's torch generator)."""
     N = means.shape[0]
-    _need(means, "means", 3 * N)
-    _need(scales, "scales", 3 * N)
-    _need(rotations, "rotations", 4 * N)
-    _need(opacities, "opacities", N)
-    if noise is not None:
-        _need(noise, "noise", 3 * N)
+    _flat_rows(("means", means, 3 * N), ("scales", scales, 3 * N), ("rotations", rotations, 4 * N), ("opacities", opacities, N),
+               ("noise", noise, 3 * N))
     if N == 0:
         return means
     if S.pending_updates:
@@ -128,8 +117,7 @@ class _MCMCRegFn(torch.autograd.Function):
     @_guarded(1)
     def forward(ctx, opacities, scales, opacity_w, scale_w, raw):
         N = opacities.numel()
-        _need(opacities, "opacities", N)
-        _need(scales, "scales", 3 * N)
+        _flat_rows(("opacities", opacities, N), ("scales", scales, 3 * N))
         out = torch.zeros((2,), dtype=torch.float32, device=opacities.device)
         if N > 0:
             partials = torch.empty((2 * L.lib().gspl_mcmc_reg_partials(N),), dtype=torch.float32, device=opacities.device)

@@ -25,25 +25,10 @@ import torch
 from torch import Tensor
 
 from .. import _lib as L
+from . import _args as A
 from ._common import _guarded
 
 TABLE_FLOATS = L.GSPL_TSDF_TABLE_FLOATS
-
-
-def _gpu_f32(t, name: str, shape=None) -> Tensor:
-    if not isinstance(t, Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{name}: the mesh ops run on the GPU only; there is no CPU fallback")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name}: float32 is needed, got {t.dtype}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
-    return t
-
-
-def _same_device(t: Tensor, name: str, like: Tensor) -> Tensor:
-    if t.device != like.device:
-        raise RuntimeError(f"{name} must be on the state's device ({like.device}), got {t.device}")
-    return t
 
 
 def _floats(value, n: int, name: str, device) -> Tensor:
@@ -102,32 +87,30 @@ def tsdf_fuse(state, table: Tensor, views: Tensor, depth: Tensor, rgb: Optional[
     """Fuse `depth` [V, H, W] (and `rgb` [V, 3, H, W]) seen through `views` [V, 4, 4] (or [V, 16]) into state = (tsdf, weight, color),
     in place; returns the state.  See the module text and header section 18."""
     tsdf, weight, color = state
-    _gpu_f32(tsdf, "tsdf")
-    if tsdf.dim() != 1:
-        raise ValueError(f"tsdf must be [M], got {list(tsdf.shape)}")
+    A.gpu_f32("mesh", "tsdf", tsdf, ("M",))
     M = tsdf.shape[0]
-    _same_device(_gpu_f32(weight, "weight", (M,)), "weight", tsdf)
+    A.gpu_f32("mesh", "weight", weight, (M,), tsdf, "tsdf")
     if color is not None:
-        _same_device(_gpu_f32(color, "color", (M, 3)), "color", tsdf)
-    _same_device(_gpu_f32(table, "table", (TABLE_FLOATS,)), "table", tsdf)
-    _same_device(_gpu_f32(depth, "depth"), "depth", tsdf)
+        A.gpu_f32("mesh", "color", color, (M, 3), tsdf, "tsdf")
+    A.gpu_f32("mesh", "table", table, (TABLE_FLOATS,), tsdf, "tsdf")
+    A.gpu_f32("mesh", "depth", depth, None, tsdf, "tsdf")
     if depth.dim() == 4 and depth.shape[1] == 1:
         depth = depth[:, 0]
     if depth.dim() != 3:
         raise ValueError(f"depth must be [V, H, W] (or [V, 1, H, W]), got {list(depth.shape)}")
     V, H, W = depth.shape
-    _same_device(_gpu_f32(views, "views"), "views", tsdf)
+    A.gpu_f32("mesh", "views", views, None, tsdf, "tsdf")
     if views.numel() != V * 16 or views.shape[0] != V:
         raise ValueError(f"views must be [{V}, 4, 4] (or [{V}, 16]), got {list(views.shape)}")
     if V > 0 and (H < 1 or W < 1):
         raise ValueError(f"depth maps must not be empty, got {list(depth.shape)}")
     if rgb is not None:
-        _same_device(_gpu_f32(rgb, "rgb", (V, 3, H, W)), "rgb", tsdf)
-    for t, name in ((tsdf, "tsdf"), (weight, "weight"), (color, "color")):
-        if t is not None and not t.is_contiguous():
-            raise ValueError(f"{name} is updated in place and must be contiguous")
+        A.gpu_f32("mesh", "rgb", rgb, (V, 3, H, W), tsdf, "tsdf")
+    for t, name in ((tsdf, "tsdf"), (weight, "weight"), (color, "color")):      # (updated in place)
+        if t is not None:
+            A.contiguous(None, name, t, error=ValueError)
     if points is not None:
-        _same_device(_gpu_f32(points, "points", (M, 3)), "points", tsdf)
+        A.gpu_f32("mesh", "points", points, (M, 3), tsdf, "tsdf")
         n = b = m = (0, 0, 0)
     else:
         if lattice is None:
@@ -167,9 +150,7 @@ def _soup(volume, level, grid, G, b):
 @torch.no_grad()
 def marching_tetrahedra_soup(volume: Tensor, level: float, origin, step, global_dims=None, block_offset=None) -> Tuple[Tensor, Tensor]:
     """(vertices [3 T, 3], keys [3 T]) in emission order: cell-major, then tetrahedron, then triangle (header section 18)."""
-    _gpu_f32(volume, "volume")
-    if volume.dim() != 3:
-        raise ValueError(f"volume must be [X, Y, Z], got {list(volume.shape)}")
+    A.gpu_f32("mesh", "volume", volume, ("X", "Y", "Z"))
     G = tuple(volume.shape) if global_dims is None else _ints3(global_dims, "global_dims")
     b = (0, 0, 0) if block_offset is None else _ints3(block_offset, "block_offset")
     if min(b) < 0 or any(bb + s > g for bb, s, g in zip(b, volume.shape, G)):

@@ -21,17 +21,10 @@ from torch import Tensor
 from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
+from . import _args as A
 from ._common import _guarded, _f32c
 
 _CONSTANTS: dict = {}
-
-
-def _rows_gpu(t: Tensor, name: str, n: int, width: int) -> Tensor:
-    if not isinstance(t, Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{name}: the PVG ops run on the GPU only; there is no CPU fallback")
-    if t.numel() != n * width or (t.dim() == 2 and t.shape[1] != width) or t.dim() not in (1, 2) or (width == 3 and t.dim() != 2):
-        raise ValueError(f"{name} must be [{n}, {width}]" + (f" or [{n}]" if width == 1 else "") + f", got {list(t.shape)}")
-    return t
 
 
 def _filled(values, device) -> Tensor:
@@ -97,11 +90,12 @@ def pvg_motion(means: Tensor, velocity: Tensor, t: Tensor, scale_t: Tensor, opac
     if not isinstance(means, Tensor) or means.dim() != 2 or means.shape[1] != 3:
         raise ValueError(f"means must be [N, 3], got {list(getattr(means, 'shape', ()))}")
     N = means.shape[0]
-    _rows_gpu(means, "means", N, 3)
-    _rows_gpu(velocity, "velocity", N, 3)
-    rows = [_rows_gpu(x, name, N, 1) for x, name in ((t, "t"), (scale_t, "scale_t"), (opacities, "opacities"))]
+    for name, x, width in (("means", means, 3), ("velocity", velocity, 3), ("t", t, 1), ("scale_t", scale_t, 1), ("opacities", opacities, 1)):
+        A.on_gpu(None, name, x, family="PVG")
+        if x.numel() != N * width or (x.dim() == 2 and x.shape[1] != width) or x.dim() not in (1, 2) or (width == 3 and x.dim() != 2):
+            raise ValueError(f"{name} must be [{N}, {width}]" + (f" or [{N}]" if width == 1 else "") + f", got {list(x.shape)}")
     if not float(cycle) > 0:
         raise ValueError(f"cycle must be positive, got {cycle}")
     table = motion_table(time, time_offset, time_shift, cycle, velocity_decay, means.device)
     # ([N] rows come back as [N] gradients, [N, 1] rows as [N, 1]: the autograd function keeps the shape it was given)
-    return _PvgMotionFn.apply(_f32c(means), _f32c(velocity), *[_f32c(x) for x in rows], table)
+    return _PvgMotionFn.apply(_f32c(means), _f32c(velocity), *[_f32c(x) for x in (t, scale_t, opacities)], table)

@@ -20,7 +20,7 @@ import torch
 from torch import Tensor
 
 from .. import _lib as L
-from . import _frame
+from . import _args as A, _frame
 from ._common import _guarded
 
 MAX_S = 4096
@@ -30,20 +30,8 @@ MAX_C = 64
 MAX_DIM = 16384
 
 
-def _device_tensor(who: str, name: str, t, dtypes, like: Optional[Tensor] = None) -> Tensor:
-    if not isinstance(t, Tensor):
-        raise TypeError(f"{who}: {name} must be a tensor")
-    if not t.is_cuda:
-        raise RuntimeError(f"{who}: {name} must be on the GPU; there is no CPU fallback")
-    if like is not None and t.device != like.device:
-        raise RuntimeError(f"{who}: {name} is on {t.device}, not on {like.device}")
-    if t.dtype not in dtypes:
-        raise NotImplementedError(f"{who}: {name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
-    return t.detach().contiguous()
-
-
 def _masks(who: str, masks) -> Tuple[Tensor, int, int, int]:
-    m = _device_tensor(who, "masks", masks, (torch.bool, torch.uint8))
+    m = A.gpu_tensor(who, "masks", masks, torch.bool, torch.uint8).detach().contiguous()
     if m.dim() != 3:
         raise ValueError(f"{who}: masks must be [N, H, W], got {tuple(m.shape)}")
     N, H, W = m.shape
@@ -55,14 +43,14 @@ def _masks(who: str, masks) -> Tuple[Tensor, int, int, int]:
 
 
 def _order(who: str, order, N: int, like: Tensor) -> Tensor:
-    o = _device_tensor(who, "order", order, (torch.int32, torch.int64), like)
+    o = A.gpu_tensor(who, "order", order, torch.int32, torch.int64, like=like).detach().contiguous()
     if tuple(o.shape) != (N,):
         raise ValueError(f"{who}: order must be [{N}], got {tuple(o.shape)}")
     return o.to(torch.int32)
 
 
 def _pixel_index(who: str, pixel_index, like: Tensor) -> Tensor:
-    p = _device_tensor(who, "pixel_index", pixel_index, (torch.int32, torch.int64), like)
+    p = A.gpu_tensor(who, "pixel_index", pixel_index, torch.int32, torch.int64, like=like).detach().contiguous()
     if p.dim() != 1 or not 1 <= p.numel() <= MAX_S:
         raise NotImplementedError(f"{who}: pixel_index must be [S] with 1 <= S <= {MAX_S}, got {tuple(p.shape)}")
     return p.to(torch.int32)
@@ -110,15 +98,15 @@ def segany_pair_labels(bits: Tensor, scale_index: Tensor, upper: Tensor, n_masks
     Bit n of labels[h, j] = gt_corrs[n, h, j]; the matrix is symmetric and both triangles are written.  counts, over the full matrix
     with the diagonal: pairs labelled 1 at no scale, at every scale, and the rest.  Integers throughout: exact."""
     who = "segany_pair_labels"
-    b = _device_tensor(who, "bits", bits, (torch.int64,))
+    b = A.gpu_tensor(who, "bits", bits, torch.int64).detach().contiguous()
     if b.dim() != 2 or not 1 <= b.shape[0] <= MAX_S or not 1 <= b.shape[1] <= MAX_MASKS // 64:
         raise NotImplementedError(f"{who}: bits must be [S <= {MAX_S}, NW <= {MAX_MASKS // 64}], got {tuple(b.shape)}")
     S, NW = b.shape
     N = 64 * NW if n_masks is None else int(n_masks)
     if (N + 63) // 64 != NW:
         raise ValueError(f"{who}: {N} masks need {(N + 63) // 64} words, bits has {NW}")
-    si = _device_tensor(who, "scale_index", scale_index, (torch.int32, torch.int64), b).to(torch.int32)
-    up = _device_tensor(who, "upper", upper, (torch.bool, torch.uint8), b).view(torch.uint8)
+    si = A.gpu_tensor(who, "scale_index", scale_index, torch.int32, torch.int64, like=b).detach().contiguous().to(torch.int32)
+    up = A.gpu_tensor(who, "upper", upper, torch.bool, torch.uint8, like=b).detach().contiguous().view(torch.uint8)
     Ns = si.numel()
     if si.dim() != 1 or up.shape != si.shape or not 1 <= Ns <= MAX_SCALES:
         raise NotImplementedError(f"{who}: scale_index and upper must be [Ns] with 1 <= Ns <= {MAX_SCALES}, got {tuple(si.shape)}, {tuple(up.shape)}")
@@ -139,7 +127,7 @@ class SeganyLossState(NamedTuple):
 
 
 def _loss_inputs(who, rendered, mask_hw, pixel_index, gates, labels, counts, a, rand):
-    r = _device_tensor(who, "rendered", rendered, (torch.float32,))
+    r = A.gpu_tensor(who, "rendered", rendered, torch.float32).detach().contiguous()
     if r.dim() != 3:
         raise ValueError(f"{who}: rendered must be [C, H, W], got {tuple(r.shape)}")
     C, Hr, Wr = r.shape
@@ -150,18 +138,18 @@ def _loss_inputs(who, rendered, mask_hw, pixel_index, gates, labels, counts, a, 
         raise NotImplementedError(f"{who}: every image dimension must be 1 .. {MAX_DIM}, got {(Hr, Wr)} and {(mh, mw)}")
     p = _pixel_index(who, pixel_index, r)
     S = p.numel()
-    g = _device_tensor(who, "gates", gates, (torch.float32,), r)
+    g = A.gpu_tensor(who, "gates", gates, torch.float32, like=r).detach().contiguous()
     if g.dim() != 2 or g.shape[1] != C or not 1 <= g.shape[0] <= MAX_SCALES:
         raise NotImplementedError(f"{who}: gates must be [Ns <= {MAX_SCALES}, {C}], got {tuple(g.shape)}")
     Ns = g.shape[0]
-    lab = _device_tensor(who, "labels", labels, (torch.uint16,), r)
-    cnt = _device_tensor(who, "counts", counts, (torch.int32,), r)
-    av = _device_tensor(who, "a", a, (torch.float32,), r)
+    lab = A.gpu_tensor(who, "labels", labels, torch.uint16, like=r).detach().contiguous()
+    cnt = A.gpu_tensor(who, "counts", counts, torch.int32, like=r).detach().contiguous()
+    av = A.gpu_tensor(who, "a", a, torch.float32, like=r).detach().contiguous()
     if tuple(lab.shape) != (S, S) or tuple(cnt.shape) != (3,) or tuple(av.shape) != (S,):
         raise ValueError(f"{who}: labels must be [{S}, {S}], counts [3], a [{S}]; got {tuple(lab.shape)}, {tuple(cnt.shape)}, {tuple(av.shape)}")
     rnd = None
     if rand is not None:
-        rnd = _device_tensor(who, "rand", rand, (torch.float32,), r)
+        rnd = A.gpu_tensor(who, "rand", rand, torch.float32, like=r).detach().contiguous()
         if tuple(rnd.shape) != (S, S):
             raise ValueError(f"{who}: rand must be [{S}, {S}], got {tuple(rnd.shape)}")
     return r, (S, C, Ns, Hr, Wr, mh, mw), p, g, lab, cnt, av, rnd
@@ -203,10 +191,10 @@ def segany_loss_backward(state: SeganyLossState, rendered_shape, mask_hw, pixel_
     Hr, Wr = int(rendered_shape[-2]), int(rendered_shape[-1])
     mh, mw = int(mask_hw[0]), int(mask_hw[1])
     p = _pixel_index(who, pixel_index, F)
-    g = _device_tensor(who, "gates", gates, (torch.float32,), F)
-    lab = _device_tensor(who, "labels", labels, (torch.uint16,), F)
-    av = _device_tensor(who, "a", a, (torch.float32,), F)
-    go = _device_tensor(who, "grad_out", grad_out, (torch.float32,), F)
+    g = A.gpu_tensor(who, "gates", gates, torch.float32, like=F).detach().contiguous()
+    lab = A.gpu_tensor(who, "labels", labels, torch.uint16, like=F).detach().contiguous()
+    av = A.gpu_tensor(who, "a", a, torch.float32, like=F).detach().contiguous()
+    go = A.gpu_tensor(who, "grad_out", grad_out, torch.float32, like=F).detach().contiguous()
     Ns = g.shape[0]
     if (p.numel() != S or g.dim() != 2 or g.shape[1] != C or tuple(lab.shape) != (S, S) or tuple(av.shape) != (S,) or go.numel() != 1
             or tuple(state.selected.shape) != (S, S) or tuple(state.sel_counts.shape) != (2,)):

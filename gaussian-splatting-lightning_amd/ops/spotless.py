@@ -17,6 +17,7 @@ import torch
 from torch import Tensor
 
 from .. import _lib as L
+from . import _args
 from ._common import _guarded
 
 HIDDEN = 16
@@ -26,23 +27,12 @@ MAX_BINS = 15360
 _EDGES: dict = {}
 
 
-def _check_table(who: str, name: str, t, like: Optional[Tensor] = None, aligned: bool = True):
-    if not isinstance(t, Tensor):
-        raise TypeError(f"{who}: {name} must be a tensor")
-    if not t.is_cuda:
-        raise RuntimeError(f"{who}: {name} must be on the GPU; there is no CPU fallback")
-    if like is not None and t.device != like.device:
-        raise RuntimeError(f"{who}: {name} is on {t.device}, G on {like.device}")
-    if t.dtype != torch.float32:
-        raise NotImplementedError(f"{who}: {name} must be float32 (the only dtype built), got {t.dtype}")
-    if aligned and t.is_contiguous() and t.data_ptr() % 16:      # (a non-contiguous table is copied, as ops.hexplane_encode does)
-        raise ValueError(f"{who}: {name} must be aligned to 16 bytes (a view into the middle of another tensor?)")
-
-
 def _mask_shapes(who: str, G: Tensor, A: Tensor, B: Tensor, w2: Tensor, b2: Tensor, out_size):
     """Every check of the mask op's inputs (device, dtype, alignment, shapes) -> h0, w0, mh, mw, H, W as the entry points take them."""
     for name, t in (("G", G), ("A", A), ("B", B), ("w2", w2), ("b2", b2)):
-        _check_table(who, name, t, None if name == "G" else G, aligned=name in ("G", "A", "B"))
+        _args.gpu_tensor(who, name, t, torch.float32, like=None if name == "G" else G, like_name="G")
+        if name in ("G", "A", "B"):      # (a non-contiguous table is copied, as ops.hexplane_encode does)
+            _args.aligned16(who, name, t)
     if G.dim() != 3 or A.dim() != 2 or B.dim() != 2:
         raise ValueError(f"{who}: G must be [h0, w0, {HIDDEN}], A [mh, {HIDDEN}], B [mw, {HIDDEN}]; got {tuple(G.shape)}, {tuple(A.shape)}, {tuple(B.shape)}")
     widths = {G.shape[2], A.shape[1], B.shape[1], w2.numel()}
@@ -68,10 +58,7 @@ def spotless_mask_forward(G: Tensor, A: Tensor, B: Tensor, w2: Tensor, b2: Tenso
     """The forward launch alone, outside autograd (written into `out` when one is given: contiguous float32 of the result's shape)."""
     h0, w0, mh, mw, H, W = _mask_shapes("spotless_mask", G, A, B, w2, b2, out_size)
     shape = (H, W) if H else (mh, mw)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=G.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != G.device:
-        raise ValueError(f"spotless_mask_forward: out must be float32 {shape} on {G.device}, got {out.dtype} {tuple(out.shape)}")
+    out = _args.out("spotless_mask_forward", "out", out, shape, torch.float32, G, contiguous=False)
     L.call("gspl_spotless_mask_fwd", h0, w0, mh, mw, H, W, L.ptr(G, torch.float32), L.ptr(A, torch.float32), L.ptr(B, torch.float32),
            L.ptr(w2, torch.float32), L.ptr(b2, torch.float32), L.ptr(out), L.stream())
     return out
@@ -87,13 +74,8 @@ def spotless_mask_backward(G: Tensor, A: Tensor, B: Tensor, w2: Tensor, b2: Tens
     if not isinstance(v_out, Tensor) or tuple(v_out.shape) != shape or v_out.device != G.device:
         raise ValueError(f"spotless_mask_backward: v_out must be {shape} on {G.device}, got {tuple(v_out.shape)} on {v_out.device}")
     v = v_out.to(torch.float32).contiguous()
-    v_G = torch.empty_like(G) if v_G is None else v_G
-    v_A = torch.empty_like(A) if v_A is None else v_A
-    v_B = torch.empty_like(B) if v_B is None else v_B
-    v_w = torch.empty((HIDDEN + 1,), dtype=torch.float32, device=G.device) if v_w is None else v_w
-    for name, got, like in (("v_G", v_G, G.shape), ("v_A", v_A, A.shape), ("v_B", v_B, B.shape), ("v_w", v_w, (HIDDEN + 1,))):
-        if tuple(got.shape) != tuple(like) or got.dtype != torch.float32 or got.device != G.device:
-            raise ValueError(f"spotless_mask_backward: {name} must be float32 {tuple(like)} on {G.device}, got {got.dtype} {tuple(got.shape)}")
+    v_G, v_A, v_B, v_w = (_args.out("spotless_mask_backward", name, got, like, torch.float32, G, contiguous=False) for name, got, like in
+                          (("v_G", v_G, G.shape), ("v_A", v_A, A.shape), ("v_B", v_B, B.shape), ("v_w", v_w, (HIDDEN + 1,))))
     nbytes = L.lib().gspl_spotless_mask_workspace_bytes(h0, w0, mh, mw)
     workspace = torch.empty((nbytes,), dtype=torch.uint8, device=G.device)
     L.call("gspl_spotless_mask_bwd", h0, w0, mh, mw, H, W, L.ptr(G, torch.float32), L.ptr(A, torch.float32), L.ptr(B, torch.float32),
@@ -138,17 +120,14 @@ def _edges(bins: int, device) -> Tensor:
     return _EDGES[key]
 
 
-def _check_image(who: str, name: str, t, like: Optional[Tensor] = None, channels: bool = True):
-    if not isinstance(t, Tensor):
-        raise TypeError(f"{who}: {name} must be a tensor")
-    if not t.is_cuda:
-        raise RuntimeError(f"{who}: {name} must be on the GPU; there is no CPU fallback")
-    if t.dtype != torch.float32:
-        raise NotImplementedError(f"{who}: {name} must be float32 (the only dtype built), got {t.dtype}")
-    if channels and (t.dim() != 3 or t.shape[0] != 3):
-        raise ValueError(f"{who}: {name} must be [3, H, W], got {tuple(t.shape)}")
-    if like is not None and (t.device != like.device or tuple(t.shape[-2:]) != tuple(like.shape[-2:])):
-        raise ValueError(f"{who}: {name} must be {tuple(like.shape[-2:])} on {like.device}, got {tuple(t.shape)} on {t.device}")
+def _images(who: str, render, gt, *mask):
+    """render and gt [3, H, W] (and a mask [H, W] or [1, H, W]): float32 on the GPU, of render's size and on its device."""
+    for name, t in (("render", render), ("gt", gt)) + tuple(("mask", m) for m in mask):
+        _args.gpu_tensor(who, name, t, torch.float32)
+        if name != "mask":
+            _args.shape(who, name, t, (3, "H", "W"))
+        if t.device != render.device or tuple(t.shape[-2:]) != tuple(render.shape[-2:]):
+            raise ValueError(f"{who}: {name} must be {tuple(render.shape[-2:])} on {render.device}, got {tuple(t.shape)} on {t.device}")
 
 
 @_guarded(0)
@@ -161,8 +140,7 @@ def spotless_error_stats(render: Tensor, gt: Tensor, thresholds: Tensor, bins: i
     One clear of `counts` and one launch; nothing is read by the host.  No gradient flows through any of the four.  `out`: the four
     buffers to write into (contiguous, of those shapes and dtypes)."""
     who = "spotless_error_stats"
-    _check_image(who, "render", render)
-    _check_image(who, "gt", gt, render)
+    _images(who, render, gt)
     bins = int(bins)
     if not 1 <= bins <= MAX_BINS:
         raise NotImplementedError(f"{who}: 1 .. {MAX_BINS} bins are built, got {bins}")
@@ -179,8 +157,7 @@ def spotless_error_stats(render: Tensor, gt: Tensor, thresholds: Tensor, bins: i
         err, counts, lower, upper = out
         for name, got, shape, dtype in (("err", err, (H, W), torch.float32), ("counts", counts, (bins,), torch.int32),
                                         ("lower_mask", lower, (H, W), torch.float32), ("upper_mask", upper, (H, W), torch.float32)):
-            if tuple(got.shape) != shape or got.dtype != dtype or got.device != r.device:
-                raise ValueError(f"{who}: out's {name} must be {dtype} {shape} on {r.device}, got {got.dtype} {tuple(got.shape)}")
+            _args.buffer(who, f"out's {name}", got, shape, dtype, r, contiguous=False)
         counts.zero_()
     L.call("gspl_spotless_error_stats", H, W, bins, L.ptr(r), L.ptr(g), L.ptr(t), L.ptr(_edges(bins, r.device)), L.ptr(err, torch.float32),
            L.ptr(counts, torch.int32), L.ptr(lower, torch.float32), L.ptr(upper, torch.float32), L.stream())
@@ -188,18 +165,11 @@ def spotless_error_stats(render: Tensor, gt: Tensor, thresholds: Tensor, bins: i
 
 
 def _check_l1(who: str, render, gt, mask):
-    _check_image(who, "render", render)
-    _check_image(who, "gt", gt, render)
-    _check_image(who, "mask", mask, render, channels=False)
+    _images(who, render, gt, mask)
     if mask.numel() != render.shape[1] * render.shape[2]:
         raise ValueError(f"{who}: mask must be [H, W] or [1, H, W], got {tuple(mask.shape)}")
     if max(render.shape[1:]) > MAX_DIM or min(render.shape[1:]) < 1:
         raise NotImplementedError(f"{who}: H and W must be 1 .. {MAX_DIM}, got {tuple(render.shape[1:])}")
-
-
-def _check_buffer(who: str, name: str, t, shape, like: Tensor):
-    if not isinstance(t, Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or t.device != like.device:
-        raise ValueError(f"{who}: {name} must be float32 {tuple(shape)} on {like.device}")
 
 
 @_guarded(0)
@@ -209,10 +179,7 @@ def spotless_masked_l1_forward(render: Tensor, gt: Tensor, mask: Tensor, out: Te
     who = "spotless_masked_l1_forward"
     _check_l1(who, render, gt, mask)
     H, W = render.shape[1], render.shape[2]
-    if out is None:
-        out = torch.empty((1,), dtype=torch.float32, device=render.device)
-    else:
-        _check_buffer(who, "out", out, (1,), render)
+    out = _args.out(who, "out", out, (1,), torch.float32, render, contiguous=False)
     partials = torch.empty((L.lib().gspl_spotless_l1_partials(H * W),), dtype=torch.float32, device=render.device)
     L.call("gspl_spotless_masked_l1_fwd", H, W, L.ptr(render, torch.float32), L.ptr(gt, torch.float32), L.ptr(mask, torch.float32),
            L.ptr(partials), L.ptr(out, torch.float32), L.stream())
@@ -224,12 +191,9 @@ def spotless_masked_l1_backward(render: Tensor, gt: Tensor, mask: Tensor, grad_o
     """The elementwise backward launch alone: grad_out [1] on the device -> v_render [3, H, W].  Checked as the forward."""
     who = "spotless_masked_l1_backward"
     _check_l1(who, render, gt, mask)
-    _check_buffer(who, "grad_out", grad_out, (1,), render)
+    _args.buffer(who, "grad_out", grad_out, (1,), torch.float32, render, contiguous=False)
     H, W = render.shape[1], render.shape[2]
-    if v_render is None:
-        v_render = torch.empty_like(render)
-    else:
-        _check_buffer(who, "v_render", v_render, render.shape, render)
+    v_render = _args.out(who, "v_render", v_render, render.shape, torch.float32, render, contiguous=False)
     L.call("gspl_spotless_masked_l1_bwd", H, W, L.ptr(render, torch.float32), L.ptr(gt, torch.float32), L.ptr(mask, torch.float32),
            L.ptr(grad_out, torch.float32), L.ptr(v_render, torch.float32), L.stream())
     return v_render

@@ -23,26 +23,10 @@ from torch import Tensor
 from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
+from . import _args as A
 from ._common import _guarded
 
 HWC, CHW = L.GSPL_LAYOUT_HWC, L.GSPL_LAYOUT_CHW
-
-
-def _gpu_f32(t: Tensor, name: str, shape=None) -> Tensor:
-    if not isinstance(t, Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{name}: the surface ops run on the GPU only; there is no CPU fallback")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name}: float32 is needed, got {t.dtype}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
-    return t
-
-
-def _matrix(t: Tensor, name: str, like: Tensor) -> Tensor:
-    _gpu_f32(t, name, (3, 3))
-    if t.device != like.device:
-        raise RuntimeError(f"{name} must be on the maps' device ({like.device}), got {t.device}")
-    return t.detach().contiguous()
 
 
 def _map_hw(t: Tensor, name: str) -> Tuple[Tensor, int, int]:
@@ -80,9 +64,9 @@ class _DepthNormalFn(torch.autograd.Function):
 
 def depth_to_normal(depth: Tensor, rays: Tensor, normalize_rays: bool = False, channels_first: bool = False) -> Tensor:
     """The normal map of `depth` (header section 15): [H, W, 3], or [3, H, W] with channels_first."""
-    _gpu_f32(depth, "depth")
+    A.gpu_f32("surface", "depth", depth)
     d, _, _ = _map_hw(depth, "depth")
-    return _DepthNormalFn.apply(d, _matrix(rays, "rays", d), int(bool(normalize_rays)), CHW if channels_first else HWC)
+    return _DepthNormalFn.apply(d, A.gpu_f32("surface", "rays", rays, (3, 3), d, "the maps").detach().contiguous(), int(bool(normalize_rays)), CHW if channels_first else HWC)
 
 
 def gsplat_rays(camtoworld: Tensor, K: Tensor) -> Tensor:
@@ -126,11 +110,10 @@ class _SurfelMapsFn(torch.autograd.Function):
 def surfel_maps(allmap: Tensor, normal_rot: Tensor, rays: Tensor, depth_ratio: float) -> Tuple[Tensor, Tensor, Tensor]:
     """(rend_normal, surf_depth, surf_normal) of the surfel rasterizer's allmap [7, H, W] (header section 15): normal_rot [3, 3]
     takes the view-space normal planes to world space, rays [3, 3] is the stencil's A, depth_ratio blends expected and median depth."""
-    _gpu_f32(allmap, "allmap")
-    if allmap.dim() != 3 or allmap.shape[0] != 7:
-        raise ValueError(f"allmap must be [7, H, W], got {list(allmap.shape)}")
-    return _SurfelMapsFn.apply(allmap.contiguous(), _matrix(normal_rot, "normal_rot", allmap), _matrix(rays, "rays", allmap),
-                               float(depth_ratio))
+    A.gpu_f32("surface", "allmap", allmap, (7, "H", "W"))
+    normal_rot, rays = (A.gpu_f32("surface", name, t, (3, 3), allmap, "the maps").detach().contiguous()
+                        for name, t in (("normal_rot", normal_rot), ("rays", rays)))
+    return _SurfelMapsFn.apply(allmap.contiguous(), normal_rot, rays, float(depth_ratio))
 
 
 class _SurfaceRegFn(torch.autograd.Function):
@@ -163,12 +146,12 @@ class _SurfaceRegFn(torch.autograd.Function):
 
 def surface_reg(a: Tensor, b: Tensor, dist: Optional[Tensor] = None) -> Tensor:
     """out [2] = (mean over pixels of 1 - sum_c a_c b_c, mean of dist; 0 without dist), with gradients to all three (header section 15)."""
-    _gpu_f32(a, "a")
-    _gpu_f32(b, "b")
+    A.gpu_f32("surface", "a", a)
+    A.gpu_f32("surface", "b", b)
     if a.dim() != 3 or a.shape[0] != 3 or a.shape != b.shape or a.numel() == 0:
         raise ValueError(f"a and b must be two non-empty [3, H, W] maps, got {list(a.shape)} and {list(b.shape)}")
     if dist is not None:
-        _gpu_f32(dist, "dist")
+        A.gpu_f32("surface", "dist", dist)
         dist, H, W = _map_hw(dist, "dist")
         if (H, W) != tuple(a.shape[1:]):
             raise ValueError(f"dist must be [{a.shape[1]}, {a.shape[2]}] (or [1, H, W]), got {[H, W]}")
