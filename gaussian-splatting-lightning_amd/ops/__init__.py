@@ -48,6 +48,10 @@ reference's renderers call (same names, argument meaning and error behaviour):
   The partition-LoD route's per-frame front (internal/renderers/partition_lod_renderer.py:550-625: distances, thresholds, the frustum
   test, and the concatenation of the chosen levels; the module-level API is gspl_amd.lod)
       lod_select, lod_gather
+  The Taming-3DGS density controller's scoring (internal/density_controllers/taming_3dgs_density_controller.py: the nine `normalize`
+  calls of a view, each a boolean gather and a `torch.median`, the aggregate of `compute_gaussian_score`, and the PIL edge filter of
+  `get_edges`; the module-level API is gspl_amd.taming)
+      positive_medians, taming_score_accumulate_, find_edges
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -92,6 +96,7 @@ from .segany import (segany_mask_stats, segany_pack_membership, segany_pair_labe
                      segany_loss_backward, SeganyLossState, _SeganyLossFn)
 from .glossy import sh_view_opacities, sh_view_opacities_forward, sh_view_opacities_backward, _ShOpacityFn
 from .lod import lod_select, lod_gather
+from .taming import positive_medians, taming_score_accumulate_, find_edges
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

@@ -98,3 +98,36 @@ def cat_tensors_to_properties(new_properties: Dict[str, torch.Tensor], model, op
     except Exception:
         return _cat_parameters(new_properties, model, optimizers)
     return Utils.cat_tensors_to_properties(new_properties, model, optimizers)
+
+
+def _prune_parameters(mask: torch.Tensor, model, optimizers: List[torch.optim.Optimizer]) -> Dict[str, torch.nn.Parameter]:
+    """Rows removed (`mask`: True keeps a row): a name an optimizer trains gets `old[mask]` as a fresh Parameter in its group, with its
+    moments' rows; every other property of the model becomes a frozen Parameter of its kept rows (what the reference's
+    `Utils.prune_properties` does, internal/density_controllers/density_controller.py:105-146)."""
+    index = _groups_by_name(optimizers)
+    out: Dict[str, torch.nn.Parameter] = {}
+    for name, (optimizer, group) in index.items():
+        if len(group["params"]) != 1:
+            raise ValueError(f"optimizer group {name!r} holds {len(group['params'])} parameters, expected one")
+        previous = group["params"][0]
+        fresh = torch.nn.Parameter(previous[mask].requires_grad_(True))
+        state = optimizer.state.pop(previous, None)
+        if state is not None:
+            for key in ("exp_avg", "exp_avg_sq"):
+                if key in state:
+                    state[key] = state[key][mask]
+            optimizer.state[fresh] = state
+        group["params"][0] = fresh
+        out[name] = fresh
+    for name in model.property_names:
+        if name not in out:
+            out[name] = torch.nn.Parameter(model.get_property(name)[mask], requires_grad=False)
+    return out
+
+
+def prune_properties(mask: torch.Tensor, model, optimizers) -> Dict[str, torch.Tensor]:
+    try:  # pragma: no cover - only inside the reference repo (needs lightning)
+        from internal.density_controllers.density_controller import Utils  # type: ignore
+    except Exception:
+        return _prune_parameters(mask, model, optimizers)
+    return Utils.prune_properties(mask, model, optimizers)

@@ -1398,6 +1398,54 @@ int gspl_lod_gather(int P, int L, int K, int64_t R, int64_t n, const int64_t* se
                     const float* means, const float* shs, const float* opacities, const float* scales, const float* rotations,
                     float* out_means, float* out_shs, float* out_opacities, float* out_scales, float* out_rotations, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 27. The scoring arithmetic of the Taming-3DGS density controller (csrc/taming.hip).  PURELY ADDITIVE: five new entry points and two
+ *    constants, no new struct, nothing existing changes, GSPL_ABI_VERSION stays 39.  What `Taming3DGSUtils.normalize`, the aggregate of
+ *    `compute_gaussian_score` and `get_edges` + the min-max normalisation of `on_train_start` compute
+ *    (internal/density_controllers/taming_3dgs_density_controller.py:455-465, 536-553, 367-373, 138).  That arithmetic is torch code and
+ *    one documented PIL filter, so it is pinned directly (tests/taming_oracle.py against tests/golden/ref_taming.npz).  Device pointers
+ *    only, nothing is read by the host, no float atomics: two runs give the same bits.  Section 12's gspl_composite_scores supplies four
+ *    of the rows.
+ *
+ *  Rows: `rows` is a HOST array of R device pointers (1 <= R <= 16), each to N entries of 4 bytes, 4-byte aligned; is_i32[r] != 0
+ *  (host array too): the entries are int32 and stand for the value float(x).  An entry is VALID when its float32 bit pattern has the
+ *  sign clear, is not zero and is at most 0x7f800000: > 0 and not NaN, +inf included, subnormals included whatever the flush mode.
+ *  1 <= N <= 2^31 - 1; all indexing is 64-bit.  No row is written.
+ *
+ *  gspl_positive_medians: counts [R] int32 = the valid entries of each row, medians [R] = the valid entry of rank (counts - 1) / 2 in
+ *      ascending order (torch.median's lower middle; NaN when counts is 0).  An exact radix select on the bit pattern: a memset of the
+ *      counters, then three digit passes (11, 11 and 9 bits), each ONE launch over all rows (integer atomics into a histogram in LDS,
+ *      flushed by integer atomics into the row's counters in the workspace, nonzero bins only) followed by ONE launch of a workgroup
+ *      per row that scans the counters and fixes the digit holding the rank.  Plain launches in stream order; each pass reads every
+ *      row once, front to back.  workspace: gspl_positive_medians_workspace_bytes(R) bytes (0 for an R out of range).
+ *  gspl_taming_score_accumulate: ONE launch.  coeffs [R] (host), counts / medians [R] (device, of gspl_positive_medians on these rows),
+ *      w [1] (device), visible [N] u8, importance [N] read and written:
+ *          t_r = coeffs[r] * (v_r[g] / medians[r]) where v_r[g] is valid and counts[r] > 0, else 0          (quotient first, then c)
+ *          a = (..(t_0 + t_1) + ..) + t_{n_first - 1},   b = (..(t_{n_first} + t_{n_first + 1}) + ..) + t_{R - 1}
+ *          importance[g] = importance[g] + ((w * (b + a)) * (visible[g] ? 1 : 0))
+ *      every operation rounded on its own (no contraction), in this association: the reference's, with the per-Gaussian rows first
+ *      (1 <= n_first <= R; n_first == R: no second group).  As in the reference an invisible row whose sum is not finite becomes NaN.
+ *      N == 0 succeeds without a launch.
+ *  gspl_find_edges: image [3, H, W] uint8, or float32 in [0, 1] with is_float != 0, -> out [H, W] float32.  TWO launches.  A float is
+ *      quantised as torchvision's ToPILImage does, x * 255 truncated (clamped to 0 .. 255, NaN to 0: undefined in the reference);
+ *      grey = (R 19595 + G 38470 + B 7471 + 0x8000) >> 16 (PIL's L); e = 8 grey - the eight neighbours, clipped to 0 .. 255, in the
+ *      interior, e = grey on the one-pixel border (PIL's FIND_EDGES); x = e / 255; out = (x - min x) / (max x - min x), each a float32
+ *      operation.  A constant EDGE image (a black image, a constant one without an interior) gives 0 / 0 = NaN everywhere, as the reference does.  partial: n_partial >= gspl_find_edges_partials(H, W)
+ *      pairs of int32 (the workgroups' smallest and largest e; 0 for a size out of range: H, W >= 1, H W <= 2^31 - 1).
+ *  Anything else (R, n_first, N out of range, a NULL or misaligned pointer): GSPL_ERR_INVALID_ARG, nothing is launched; a workspace or
+ *  partial array too small: GSPL_ERR_WORKSPACE.
+ * ---------------------------------------------------------------------------------------- */
+#define GSPL_TAMING_MAX_ROWS 16
+#define GSPL_TAMING_MEDIAN_BINS 2048
+size_t gspl_positive_medians_workspace_bytes(int R);
+int gspl_positive_medians(int R, int64_t N, const void* const* rows, const int32_t* is_i32, int32_t* counts, float* medians,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int gspl_taming_score_accumulate(int R, int n_first, int64_t N, const void* const* rows, const int32_t* is_i32, const float* coeffs,
+                                 const int32_t* counts, const float* medians, const float* w, const uint8_t* visible,
+                                 float* importance, void* stream);
+int gspl_find_edges_partials(int H, int W);
+int gspl_find_edges(int H, int W, const void* image, int is_float, float* out, int32_t* partial, int n_partial, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
