@@ -52,6 +52,10 @@ reference's renderers call (same names, argument meaning and error behaviour):
   calls of a view, each a boolean gather and a `torch.median`, the aggregate of `compute_gaussian_score`, and the PIL edge filter of
   `get_edges`; the module-level API is gspl_amd.taming)
       positive_medians, taming_score_accumulate_, find_edges
+  The 3D half of the Mip-Splatting route (internal/models/mip_splatting.py: `compute_3d_filter`, a Python loop over every training
+  camera with two boolean-index assignments each, and `apply_3d_filter` / `apply_3d_filter_on_scales`, a dozen elementwise launches
+  every step; the module-level API is gspl_amd.mip)
+      mip_camera_table, mip_filter_3d, mip_apply_3d_filter, and the launches alone: mip_apply_3d_filter_forward / _backward
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -97,6 +101,8 @@ from .segany import (segany_mask_stats, segany_pack_membership, segany_pair_labe
 from .glossy import sh_view_opacities, sh_view_opacities_forward, sh_view_opacities_backward, _ShOpacityFn
 from .lod import lod_select, lod_gather
 from .taming import positive_medians, taming_score_accumulate_, find_edges
+from .mip import (mip_camera_table, mip_filter_3d, mip_apply_3d_filter, mip_apply_3d_filter_forward, mip_apply_3d_filter_backward, _MipApplyFn,
+                  _MipScalesFn)
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

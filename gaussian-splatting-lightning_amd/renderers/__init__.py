@@ -26,3 +26,6 @@ from .hip_gsplat_appearance_embedding_renderer import HipGSplatAppearanceEmbeddi
 from .hip_vanilla_gs4d_renderer import HipVanillaGS4DRenderer  # noqa: F401,E402
 from .hip_glossy_renderer import HipGlossyRenderer, HipGlossyRendererModule  # noqa: F401,E402
 from .hip_partition_lod_renderer import HipPartitionLoDRenderer, HipPartitionLoDRendererModule  # noqa: F401,E402
+from .hip_gsplat_mip_splatting_renderer import (HipGSplatMipSplattingRendererV2, HipGSplatMipSplattingRendererV2Module,  # noqa: F401,E402
+                                                HipMipSplattingRendererMixin, HipGSplatAppearanceEmbeddingMipRenderer,
+                                                HipGSplatAppearanceEmbeddingMipRendererModule)

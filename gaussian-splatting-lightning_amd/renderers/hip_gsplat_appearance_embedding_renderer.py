@@ -14,7 +14,8 @@ What runs where, after the warm-up:
     elementwise code.  Nothing is indexed, so no step waits for the device.
 During the warm-up the colours are the staged gsplat-v1 plugin's, bit for bit.
 
-Not built: the Mip, distributed, 2DGS and partition-LoD variants of the reference, which subclass this renderer."""
+The Mip variant is `HipGSplatAppearanceEmbeddingMipRenderer` (hip_gsplat_mip_splatting_renderer.py), which sits on this renderer.
+Not built: the distributed, 2DGS and partition-LoD variants of the reference, which subclass this renderer."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field

@@ -1446,6 +1446,51 @@ int gspl_taming_score_accumulate(int R, int n_first, int64_t N, const void* cons
 int gspl_find_edges_partials(int H, int W);
 int gspl_find_edges(int H, int W, const void* image, int is_float, float* out, int32_t* partial, int n_partial, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 28. The 3D half of Mip-Splatting (csrc/mip.hip).  PURELY ADDITIVE: three new entry points and five constants, no new struct, nothing
+ *    existing changes, GSPL_ABI_VERSION stays 39.  What `MipSplattingUtils.compute_3d_filter`, `apply_3d_filter` and
+ *    `apply_3d_filter_on_scales` compute (internal/models/mip_splatting.py:98-200).  That arithmetic is torch code, so it is pinned
+ *    directly (tests/mip_oracle.py against tests/golden/ref_mip.npz).  fp32, device pointers only, nothing is read by the host, no float
+ *    atomics: two runs give the same bits.  The 2D half (the dilation and the compensation) is section 2's projection.
+ *
+ *  gspl_mip_filter3d: means [N, 3], cameras [C, 16]: per row the world-to-camera rotation R (9, row-major), T (3), fx, fy, width,
+ *      height.  A memset of the workspace and TWO launches.  Per Gaussian (one per lane) and camera (uniform across the wave: the
+ *      table is read by uniform loads, never per lane), every operation rounded on its own, in the reference's order:
+ *          p = R x + T (per component fmaf(R2, z, fmaf(R1, y, R0 * x)) + T);  valid_depth = p.z > 0.01;  z = max(p.z, 0.001)
+ *          px = p.x / z * fx + width / 2,  py = p.y / z * fy + height / 2
+ *          valid = valid_depth && px >= -0.15f * width && px <= width * 1.15f && py >= -0.15f * height && py <= 1.15f * height
+ *          distance = min(distance, z) over the valid cameras, from 100000;  valid_any = some camera is valid
+ *      The first launch also takes the maximum of `distance` over the rows with valid_any (a wave reduction, then ONE integer
+ *      atomicMax per workgroup on the bit pattern: exact, the values are positive) and the largest positive fx (0 when there is none).
+ *      The second writes filter_3d [N] = (valid_any ? distance : that maximum) / max fx * (float)0.4472135954999579, two operations.
+ *      When NO row is valid in any camera the reference raises (max() of an empty tensor); here every row keeps 100000.
+ *      distance [N] and valid_any [N] u8 are optional outputs (NULL: not written).  workspace: GSPL_MIP_WORKSPACE_BYTES, 4-byte aligned.
+ *      1 <= N <= 2^31 - 1 and C >= 1, else GSPL_ERR_INVALID_ARG.
+ *  gspl_mip_apply_fwd: ONE launch.  scales [N, 3], opacities [N] or NULL, filter_3d [N] -> scales_out [N, 3], opacities_out [N].
+ *      s = RAW_SCALES ? exp(scales) : scales;  o = RAW_OPACITIES ? 1 / (1 + exp(-opacities)) : opacities;  f2 = filter_3d^2
+ *          scales_out_i = sqrt(s_i^2 + f2);   r_i = s_i / scales_out_i;   coef = r_0 r_1 r_2
+ *          opacities_out = o * coef with COMPENSATE, o without;  opacities NULL (COMPENSATE only): opacities_out = coef
+ *      coef is the product of three ratios <= 1, NOT the reference's sqrt(prod s_i^2 / prod (s_i^2 + f2)), whose float32 numerator is
+ *      subnormal or zero from scales of about 1e-7 on (its autograd then returns inf / NaN): equal to rounding elsewhere.  Where
+ *      f2 == 0 the scales pass unchanged and coef is exactly 1.  opacities_out NULL: only the scales are written.
+ *  gspl_mip_apply_bwd: ONE launch, recomputed from the forward's inputs.  v_scales_out [N, 3] and v_opacities_out [N] (either may be
+ *      NULL: zero) -> v_scales [N, 3] and, with opacities, v_opacities [N] (NULL: not wanted), the gradients of the inputs AS GIVEN
+ *      (raw or activated), every element written.  filter_3d gets none.
+ *  N == 0 succeeds without a launch in the two apply calls.  Unknown flag bits, RAW_OPACITIES without opacities, an opacities_out
+ *  with neither opacities nor COMPENSATE, a NULL required pointer: GSPL_ERR_INVALID_ARG, nothing is launched.
+ * ---------------------------------------------------------------------------------------- */
+#define GSPL_MIP_CAMERA_FLOATS 16
+#define GSPL_MIP_WORKSPACE_BYTES 8
+#define GSPL_MIP_RAW_SCALES 1
+#define GSPL_MIP_RAW_OPACITIES 2
+#define GSPL_MIP_COMPENSATE 4
+int gspl_mip_filter3d(int64_t N, int C, const float* means, const float* cameras, float* filter_3d, float* distance, uint8_t* valid_any,
+                      void* workspace, void* stream);
+int gspl_mip_apply_fwd(int64_t N, int flags, const float* scales, const float* opacities, const float* filter_3d, float* scales_out,
+                       float* opacities_out, void* stream);
+int gspl_mip_apply_bwd(int64_t N, int flags, const float* scales, const float* opacities, const float* filter_3d,
+                       const float* v_scales_out, const float* v_opacities_out, float* v_scales, float* v_opacities, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
