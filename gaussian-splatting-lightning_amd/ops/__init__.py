@@ -56,6 +56,9 @@ reference's renderers call (same names, argument meaning and error behaviour):
   camera with two boolean-index assignments each, and `apply_3d_filter` / `apply_3d_filter_on_scales`, a dozen elementwise launches
   every step; the module-level API is gspl_amd.mip)
       mip_camera_table, mip_filter_3d, mip_apply_3d_filter, and the launches alone: mip_apply_3d_filter_forward / _backward
+  The depth-regularisation loss (internal/metrics/inverse_depth_metrics.py `get_inverse_depth_metric`, internal/metrics/depth_metrics.py:
+  a normalisation, two masks and a mean over [H, W] in six to ten torch launches each way; the module-level API is gspl_amd.depthreg)
+      depth_loss
 
 Host side only: shape checks, buffer allocation through torch's caching allocator, stream hand-off.
 All arithmetic happens in libgspl_hip.so; nothing here falls back to PyTorch math.
@@ -103,6 +106,7 @@ from .lod import lod_select, lod_gather
 from .taming import positive_medians, taming_score_accumulate_, find_edges
 from .mip import (mip_camera_table, mip_filter_3d, mip_apply_3d_filter, mip_apply_3d_filter_forward, mip_apply_3d_filter_backward, _MipApplyFn,
                   _MipScalesFn)
+from .depthloss import depth_loss, _DepthLossFn
 from .side import radix_sort_pairs, radix_sort_keys64, distCUDA2, l1_ssim, fused_ssim, photometric_loss
 
 

@@ -1491,6 +1491,40 @@ int gspl_mip_apply_fwd(int64_t N, int flags, const float* scales, const float* o
 int gspl_mip_apply_bwd(int64_t N, int flags, const float* scales, const float* opacities, const float* filter_3d,
                        const float* v_scales_out, const float* v_opacities_out, float* v_scales, float* v_opacities, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * 29. The depth-regularisation loss (csrc/depthloss.hip).  PURELY ADDITIVE: three new entry points and six constants, no new struct,
+ *    nothing existing changes, GSPL_ABI_VERSION stays 39.  fp32, device pointers only, nothing is read by the host.
+ *
+ *  The depth loss: what HasInverseDepthMetricsModule.get_inverse_depth_metric (internal/metrics/inverse_depth_metrics.py:70-104) and
+ *  DepthMetricsModule.get_inverse_depth_metric (internal/metrics/depth_metrics.py:52-61) compute, every operation rounded on its own:
+ *      NONE    p' = p                                          MEDIAN  p' = p / median   (median[0] on the device, or median_value)
+ *      MINMAX  p' = (p - min p) / ((max p - min p) + 1e-8f)    MEAN    p' = p / mean(gt), g' = g / mean(gt)   (before the masks)
+ *      then p' and g' are both multiplied by gt_mask and by pixel_mask where given ([H, W]; float32, or bytes with *_u8 != 0);
+ *      out[0] = sum_p |g' - p'| / (H W)  (L1)  or  sum_p (g' - p')^2 / (H W)  (L2), over ALL H W elements.
+ *  gspl_depth_loss_fwd: a 16-byte memset of the workspace's head and at most TWO launches: the min / max or sum reduction (MINMAX and
+ *      MEAN only), then the elementwise pass; each leaves one partial per workgroup of 2048 elements, and the workgroup that arrives
+ *      last adds all partials in index order (agent-scope atomics for the hand-off, no float atomics): two runs give the same bits.
+ *      workspace: gspl_depth_loss_workspace_bytes(H, W) bytes, 16-byte aligned; it keeps min / max / mean for the backward.
+ *  gspl_depth_loss_bwd: one launch.  v_pred [H, W] = -(sign(g' - p') or 2 (g' - p')) (d p' / d p) grad_out[0] / (H W), every element
+ *      written, sign(0) = 0; grad_out on the device; `workspace` as the forward left it.  min, max, median, mean(gt) carry no gradient.
+ *  1 <= H W <= 2^31, else GSPL_ERR_INVALID_ARG; another `kind` (the reference's l1+ssim) is GSPL_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------------------------- */
+#define GSPL_DEPTH_LOSS_L1 0
+#define GSPL_DEPTH_LOSS_L2 1
+#define GSPL_DEPTH_NORM_NONE 0
+#define GSPL_DEPTH_NORM_MINMAX 1
+#define GSPL_DEPTH_NORM_MEDIAN 2
+#define GSPL_DEPTH_NORM_MEAN 3
+size_t gspl_depth_loss_workspace_bytes(int H, int W);
+int gspl_depth_loss_fwd(int H, int W, int kind, int normalize, const float* pred, const float* gt,
+                        const float* median, float median_value,
+                        const void* gt_mask, int gt_mask_u8, const void* pixel_mask, int pixel_mask_u8,
+                        void* workspace, size_t workspace_bytes, float* out, void* stream);
+int gspl_depth_loss_bwd(int H, int W, int kind, int normalize, const float* pred, const float* gt,
+                        const float* median, float median_value,
+                        const void* gt_mask, int gt_mask_u8, const void* pixel_mask, int pixel_mask_u8,
+                        const void* workspace, const float* grad_out, float* v_pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
